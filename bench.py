@@ -14,7 +14,14 @@ anything touches the GPU); under an outer torchrun it is one rank.
 ``--scaling weak`` (default): B clouds per GPU. ``--scaling strong``: the global
 batch B is split over the ranks, B / world per GPU (main_partseg_dist.py:165).
 
-Prints ONE JSON line on rank 0: whole-job clouds/s, plus
+A plain run sets up, warms up (``--warmup`` steps), times ``--steps`` steps and
+prints ONE JSON line on rank 0: whole-job clouds/s (``value``) and
+``ms_per_step``. ``--dump-outputs DIR`` then writes what the last timed step
+computed (dump_outputs below). Everything else is measured only with ``--full``
+(each leg has its own ``--no-*`` switch there), which adds to the line
+  eager_launch_ms_per_step / autocast_eager_ms_per_step  the same step launched
+                eagerly, and under fp16 autocast (N=1), in K-step regions of
+                their own before the headline region;
   roofline      the kNN selection kernel (the engine's largest kernel family):
                 its launches bracketed by HIP events on their own stream in a
                 second K-step region (only those launches, 8 events per step);
@@ -66,6 +73,13 @@ def parse(argv=None):
     p.add_argument("--points", type=int, default=None)
     p.add_argument("--k", type=int, default=None)
     p.add_argument("--emb", type=int, default=1024)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: the eager-launched and autocast "
+                        "steps, the kNN roofline region, the fp32 modes, the EdgeConv / PositionEmbedding / "
+                        "attention legs, the PyTorch eager and CPU baselines (each has a --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (model output, "
+                        "gradients, updated parameters and buffers of rank 0) as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-eager-baseline", action="store_true")
     p.add_argument("--cpu-reps", type=int, default=3)
@@ -94,6 +108,12 @@ def parse(argv=None):
                    help="N>1: SyncBatchNorm (global-batch BN statistics, main_partseg_dist.py:189) instead of "
                         "per-replica BN (main_cls.py:62 DataParallel semantics)")
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:   # a plain run measures the headline figure only
+        for leg in ("cpu_baseline", "eager_baseline", "fp32_leg", "edgeconv_leg", "posemb_leg", "roofline_leg",
+                    "attention_leg"):
+            setattr(a, "no_" + leg, True)
     preset = PRESETS[a.config]
     a.batch = a.batch or preset[0]
     a.points = a.points or preset[1]
@@ -475,6 +495,40 @@ def make_input(args, clouds, seed):
     return synth.cube_clouds(clouds, args.points, seed=seed)
 
 
+DUMP_SAMPLE = 1 << 22   # elements kept of an array larger than this (16 MiB as float32)
+
+
+def dump_outputs(path, y, model):
+    """--dump-outputs: what a caller of the timed step holds after the last timed
+    step, as ``path``/<name>.npy: ``output`` (the model's (B, emb, N) output),
+    ``grad.<parameter>``, and ``param.<name>`` for every state_dict entry (the
+    parameters after the SGD update, the BatchNorm buffers). float32, float64
+    for double and integer tensors. An array of more than DUMP_SAMPLE elements
+    is stored as the DUMP_SAMPLE flat elements a fixed seeded draw picks (the
+    same ones in every run), which keeps the whole dump under 64 MB. Inputs,
+    initial weights and the upstream gradient are seeded, so two runs with the
+    same arguments write comparable files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, t):
+        t = t.detach().reshape(-1) if t.numel() > DUMP_SAMPLE else t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            pick = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(4321))
+            t = t[pick.to(t.device)]
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+    save("output", y)
+    for n, p in model.named_parameters():
+        if p.grad is not None:
+            save("grad." + n, p.grad)
+    for n, t in model.state_dict().items():
+        save("param." + n, t)
+
+
 def pmc_traffic(args, shapes, per_gpu):
     """HBM bytes per kNN selection launch from the committed rocprofv3 PMC
     summary of this config (profiles/*_pmc_<config>.json, newest round first),
@@ -576,6 +630,16 @@ def main():
     x = pts.permute(0, 2, 1)  # (B,C,N) view, as main_cls.py:91 feeds the model
 
     gy = upstream_grad((per_gpu, args.emb, args.points), dev)
+    last = {}   # the model output of the latest step (a graph's static output buffer once captured)
+
+    def forward():
+        # only a detached alias is kept: holding y itself would keep the step's autograd
+        # graph alive into the next step, and with it the parameters' AccumulateGrad nodes,
+        # which stay bound to the stream they were made on (not the capturing stream)
+        y = net(x)
+        if args.dump_outputs:
+            last["y"] = y.detach()
+        return y
 
     if flat_dp:
         params = [p for p in model.parameters() if p.requires_grad]
@@ -587,7 +651,7 @@ def main():
 
         def fwd_bwd():
             flat.zero_()
-            net(x).backward(gy)
+            forward().backward(gy)
 
         def reduce_and_step():
             dist.all_reduce(flat)
@@ -600,19 +664,20 @@ def main():
     else:
         def step():
             opt.zero_grad(set_to_none=True)
-            y = net(x)
+            y = forward()
             y.backward(gy)
             opt.step()
 
     for _ in range(args.warmup):
         step()
-    # the same step launched eagerly (one C++ op + C++ autograd node issue the
-    # ~60 launches of a step: dgx.host)
-    elapsed_eager = reduce_elapsed(timed_region(step, args.steps, world), world, dev)
     launch = "eager"
     run = step
-    elapsed_amp = None
-    if world == 1 and not distributed:
+    elapsed_eager = elapsed_amp = None
+    if args.full:
+        # the same step launched eagerly (one C++ op + C++ autograd node issue the
+        # ~60 launches of a step: dgx.host)
+        elapsed_eager = reduce_elapsed(timed_region(step, args.steps, world), world, dev)
+    if args.full and world == 1 and not distributed:
         # the reference's own training configuration (main_partseg_dist.py:253): the
         # eager step under fp16 autocast with the engine's global mode at fp32 — the
         # GEMMs follow autocast to the split-bf16 path (16 significant bits per
@@ -644,8 +709,9 @@ def main():
         torch.cuda.current_stream(dev).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         opt.zero_grad(set_to_none=True)
+        last.clear()
         with torch.cuda.graph(graph):
-            net(x).backward(gy)
+            forward().backward(gy)
             opt.step()
         run = graph.replay
         for _ in range(2):
@@ -659,6 +725,7 @@ def main():
                 fwd_bwd()
         torch.cuda.current_stream(dev).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
+        last.clear()
         # thread_local: the collective backend's watchdog thread may query events
         # while this thread captures (a global capture mode would reject that)
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
@@ -672,6 +739,8 @@ def main():
         launch = "hip_graph+allreduce" + ("(+syncbn collectives in graph)" if args.sync_bn else "")
     # headline: the timed region runs uninstrumented
     elapsed = reduce_elapsed(timed_region(run, args.steps, world), world, dev)
+    if args.dump_outputs and rank == 0:   # before any further leg steps the model again
+        dump_outputs(args.dump_outputs, last["y"], model)
     result = {
         "metric": METRIC,
         "value": round(total * args.steps / elapsed, 2),
@@ -679,9 +748,11 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "launch": launch,
-        "eager_launch_ms_per_step": round(elapsed_eager / args.steps * 1e3, 3),
+        "eager_launch_ms_per_step": (round(elapsed_eager / args.steps * 1e3, 3) if elapsed_eager is not None
+                                     else None),
         "autocast_eager_ms_per_step": (round(elapsed_amp / args.steps * 1e3, 3) if elapsed_amp is not None
                                        else None),
         "replicas_in_sync": replicas_in_sync(model, world, dev, distributed),

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -16,8 +17,32 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a ROCm GPU (MI355X) and libdgx.so")
 
 
+class _GoldenParts:
+    """A fixture that make_goldens.py stored as <stem>.part<i>.npz files (each
+    under the 1 MiB limit for a committed file), read like the one .npz: the
+    arrays of all parts, in their order."""
+
+    def __init__(self, paths):
+        self._arrays = {}
+        for p in paths:
+            with np.load(p, allow_pickle=False) as z:
+                for k in z.files:
+                    assert k not in self._arrays, (p, k)
+                    self._arrays[k] = z[k]
+        self.files = list(self._arrays)
+
+    def __getitem__(self, key):
+        return self._arrays[key]
+
+
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, os.path.splitext(name)[0] + ".part[0-9].npz")))
+    if not parts:
+        raise FileNotFoundError(path)
+    return _GoldenParts(parts)
 
 
 @pytest.fixture(scope="session")

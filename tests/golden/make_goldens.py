@@ -5,7 +5,8 @@ It imports /root/reference/models (read-only; nothing is written there) and
 records inputs, outputs and gradients of the hot path as data fixtures. The
 reference's source never leaves the build container; only these vectors do.
 
-Fixtures
+Fixtures (one that would pass 900 KiB is stored as <stem>.part<i>.npz files,
+which tests/conftest.py load_golden reads under the .npz name)
   knn_cases.npz      reference knn (dgcnn.py:6-12) on synthetic clouds, C in
                      {3,9,64,128}, both memory layouts, plus a duplicate-point
                      tie set; indices in canonical order + selected pd values.
@@ -21,7 +22,9 @@ Fixtures
   hashes.json        SHA-256 of the canonical int32 kNN of the full-size bench
                      inputs (cfg2/cfg3/cfg5 first layer) + state_dict key lists.
 """
+import glob
 import hashlib
+import io
 import json
 import os
 import sys
@@ -47,6 +50,38 @@ from models.layers import PositionEmbedding as RefPosEmb  # noqa: E402
 import models.model_partseg as ref_partseg  # noqa: E402
 
 torch.set_num_threads(8)
+
+
+PART_BYTES = 900 * 1024   # a committed file stays under 1 MiB
+
+
+def save_npz(name, **arrays):
+    """np.savez_compressed, or — when that file would pass PART_BYTES — the
+    same arrays in order over <stem>.part1.npz, <stem>.part2.npz, ..., each
+    under it (tests/conftest.py load_golden reads either form)."""
+    def packed(items):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **dict(items))
+        return buf.getvalue()
+
+    items = list(arrays.items())
+    whole = packed(items)
+    stem = os.path.join(HERE, os.path.splitext(name)[0])
+    for old in glob.glob(stem + ".npz") + glob.glob(stem + ".part[0-9].npz"):
+        os.remove(old)
+    if len(whole) <= PART_BYTES:
+        parts = [whole]
+    else:
+        parts, cur = [], []
+        for item in items:
+            if cur and len(packed(cur + [item])) > PART_BYTES:
+                parts.append(packed(cur))
+                cur = []
+            cur.append(item)
+        parts.append(packed(cur))
+    for i, blob in enumerate(parts):
+        with open(stem + (".npz" if len(parts) == 1 else f".part{i + 1}.npz"), "wb") as f:
+            f.write(blob)
 
 
 def ref_pd(x):
@@ -90,7 +125,7 @@ def knn_cases():
     idx = ref_knn(x, 20)
     ci, cv = canonical(idx, ref_pd(x))
     out["ties_perm_x"], out["ties_perm_idx"], out["ties_perm_val"] = pts, ci.astype(np.int32), cv
-    np.savez_compressed(os.path.join(HERE, "knn_cases.npz"), **out)
+    save_npz("knn_cases.npz", **out)
 
 
 def graph_feature_cases():
@@ -105,7 +140,7 @@ def graph_feature_cases():
         out[name + "_knn"] = ref_ggf(inp, k=8, knn_only=True).numpy()
         ci, _ = canonical(ref_knn(inp, 8), ref_pd(inp))
         out[name + "_idx"] = ci.astype(np.int32)
-    np.savez_compressed(os.path.join(HERE, "graph_feature.npz"), **out)
+    save_npz("graph_feature.npz", **out)
 
 
 def edgeconv_block_case():
@@ -124,11 +159,11 @@ def edgeconv_block_case():
     gy = torch.from_numpy(synth.uniform(32, tuple(y.shape)) - 0.5)
     y.backward(gy)
     ci, _ = canonical(ref_knn(x.detach(), k), ref_pd(x.detach()))
-    np.savez_compressed(os.path.join(HERE, "edgeconv_block.npz"), x=x.detach().numpy(), idx=ci.astype(np.int32),
-                        weight=w0.numpy(), gamma=g0.numpy(), beta=b0.numpy(), k=k, out=y.detach().numpy(),
-                        gout=gy.numpy(), dx=x.grad.numpy(), dweight=block[0].weight.grad.numpy(),
-                        dgamma=block[1].weight.grad.numpy(), dbeta=block[1].bias.grad.numpy(),
-                        running_mean=block[1].running_mean.numpy(), running_var=block[1].running_var.numpy())
+    save_npz("edgeconv_block.npz", x=x.detach().numpy(), idx=ci.astype(np.int32),
+             weight=w0.numpy(), gamma=g0.numpy(), beta=b0.numpy(), k=k, out=y.detach().numpy(),
+             gout=gy.numpy(), dx=x.grad.numpy(), dweight=block[0].weight.grad.numpy(),
+             dgamma=block[1].weight.grad.numpy(), dbeta=block[1].bias.grad.numpy(),
+             running_mean=block[1].running_mean.numpy(), running_var=block[1].running_var.numpy())
 
 
 def dgcnn_case():
@@ -144,8 +179,8 @@ def dgcnn_case():
     grads = {"grad." + n: p.grad.numpy() for n, p in model.named_parameters()}
     after = {"after." + k_: v.numpy() for k_, v in model.state_dict().items() if "running" in k_}
     init = {"init." + k_: v for k_, v in state0.items()}
-    np.savez_compressed(os.path.join(HERE, "dgcnn_small.npz"), x=x.contiguous().numpy(), out=y.detach().numpy(),
-                        gout=gy.numpy(), **init, **grads, **after)
+    save_npz("dgcnn_small.npz", x=x.contiguous().numpy(), out=y.detach().numpy(),
+             gout=gy.numpy(), **init, **grads, **after)
 
 
 def posemb_case():
@@ -174,8 +209,8 @@ def posemb_case():
                                               np.linalg.norm(p.grad.numpy().astype(np.float64))])
         else:
             grads["grad." + n] = p.grad.numpy()
-    np.savez_compressed(os.path.join(HERE, "posemb_small.npz"), x=x.numpy(), out=y.detach().numpy(),
-                        gout=gy.numpy(), init_sha256=np.array(init_sha), **grads, **proj)
+    save_npz("posemb_small.npz", x=x.numpy(), out=y.detach().numpy(),
+             gout=gy.numpy(), init_sha256=np.array(init_sha), **grads, **proj)
 
 
 PARTSEG_BIG = ("pos_mlp.0.conv3.0.weight", "pos_mlp.0.linear.0.weight")
@@ -219,8 +254,8 @@ def partseg_case():
             grads["gradproj." + n] = np.array([(gr * r).sum(), np.linalg.norm(gr)])
     finally:
         ref_partseg.compute_hog_1x1 = orig
-    np.savez_compressed(os.path.join(HERE, "partseg_small.npz"), x=x.numpy(), hog=hog.numpy(), lbl=lbl.numpy(),
-                        out=y.detach().numpy(), gout=gy.numpy(), **state0, **grads)
+    save_npz("partseg_small.npz", x=x.numpy(), hog=hog.numpy(), lbl=lbl.numpy(),
+             out=y.detach().numpy(), gout=gy.numpy(), **state0, **grads)
 
 
 def hashes():

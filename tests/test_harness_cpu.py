@@ -5,6 +5,7 @@ names), data.* datasets (synthetic stand-ins: shapes, dtypes, augmentations)."""
 import types
 
 import numpy as np
+import pytest
 import torch
 
 
@@ -138,3 +139,20 @@ def test_bench_pmc_traffic_only_for_preset_shapes():
     args = types.SimpleNamespace(config="cfg2", points=1024, k=20, batch=4)
     traffic, note = bench.pmc_traffic(args, [3, 64, 64, 128], 4)
     assert traffic is None and "no PMC profile for B=4" in note
+
+
+LEGS = ("cpu_baseline", "eager_baseline", "fp32_leg", "edgeconv_leg", "posemb_leg", "roofline_leg", "attention_leg")
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain bench.py run switches every extra leg off; --full leaves each to
+    its own --no-* switch; --steps is the number of timed steps as given."""
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs is None and (plain.steps, plain.warmup) == (7, 2)
+    assert all(getattr(plain, "no_" + leg) for leg in LEGS)
+    full = bench.parse(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert full.full and full.dump_outputs == "out" and full.no_cpu_baseline
+    assert not any(getattr(full, "no_" + leg) for leg in LEGS[1:])
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

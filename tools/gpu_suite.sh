@@ -14,7 +14,7 @@ export PYTHONDONTWRITEBYTECODE=1
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "$@" \
     > "$OUT/${TAG}_pytest_gpu.log" 2>&1 || { echo "pytest failed rc=$?"; tail -30 "$OUT/${TAG}_pytest_gpu.log"; exit 1; }
 tail -2 "$OUT/${TAG}_pytest_gpu.log"
-timeout -k 10 300 python -u bench.py > "$OUT/${TAG}_bench.log" 2>&1 || { echo "bench failed rc=$?"; tail -20 "$OUT/${TAG}_bench.log"; exit 1; }
+timeout -k 10 300 python -u bench.py --full > "$OUT/${TAG}_bench.log" 2>&1 || { echo "bench failed rc=$?"; tail -20 "$OUT/${TAG}_bench.log"; exit 1; }
 tail -c 400 "$OUT/${TAG}_bench.log"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof" -o run -- python3 "$ROOT/bench.py" --steps 10 \

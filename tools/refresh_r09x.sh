@@ -4,7 +4,7 @@
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT" || exit 1
-NOL="--no-roofline-leg --no-fp32-leg --no-edgeconv-leg --no-posemb-leg --no-attention-leg --no-cpu-baseline"
+NOL="--full --no-roofline-leg --no-fp32-leg --no-edgeconv-leg --no-posemb-leg --no-attention-leg --no-cpu-baseline"
 bash tools/profile.sh r09x > gpurun_out/r09x_profile.log 2>&1 || { echo "profile failed"; tail -20 gpurun_out/r09x_profile.log; exit 1; }
 tail -3 gpurun_out/r09x_profile.log
 bash tools/gpu_run.sh 300 \
