@@ -610,6 +610,41 @@ int dgx_sgd_step_f32(int n, float* const* params, const float* const* grads, flo
                      const int64_t* numels, float lr, float weight_decay, float momentum, float dampening,
                      int nesterov, int maximize, int first, void* stream);
 
+/* ---- GradScaler state, shared by the three entry points below: grad_scale
+ * and found_inf are optional device pointers to one fp32 each (torch's
+ * optimizer.grad_scale / optimizer.found_inf). With grad_scale the gradient is
+ * divided by *grad_scale on load (the stored gradient stays scaled); with
+ * *found_inf != 0 the call writes nothing at all, as torch's fused optimizers
+ * do (aten/src/ATen/native/cuda/FusedSgdKernel.cu, fused_adam_utils.cuh). */
+
+/* dgx_sgd_step_f32's update with the scaler state. */
+int dgx_sgd_step_amp_f32(int n, float* const* params, const float* const* grads, float* const* momentum_bufs,
+                         const int64_t* numels, float lr, float weight_decay, float momentum, float dampening,
+                         int nesterov, int maximize, int first, const float* grad_scale, const float* found_inf,
+                         void* stream);
+
+/* torch.optim.Adam / AdamW's update (torch/optim/adam.py, _single_tensor_adam,
+ * non-capturable branch, in fp32) over n <= 48 fp32 tensors in one launch,
+ * plus a one-workgroup launch that advances the step counts. steps[t] points
+ * to a device fp32 scalar holding the steps tensor t has taken (torch's fused
+ * state["step"]); the update computes with that value + 1, its bias
+ * corrections 1 - beta^step in double. lr_dev, if not NULL, is a device fp32
+ * scalar read in place of lr (a captured graph follows a scheduler).
+ * decoupled_weight_decay != 0 is AdamW (p *= 1 - lr * wd), otherwise
+ * g += wd * p. max_exp_avg_sqs is read only with amsgrad != 0. */
+int dgx_adam_step_f32(int n, float* const* params, const float* const* grads, float* const* exp_avgs,
+                      float* const* exp_avg_sqs, float* const* max_exp_avg_sqs, float* const* steps,
+                      const int64_t* numels, float lr, const float* lr_dev, double beta1, double beta2, double eps,
+                      double weight_decay, int decoupled_weight_decay, int amsgrad, int maximize,
+                      const float* grad_scale, const float* found_inf, void* stream);
+
+/* torch._amp_foreach_non_finite_check_and_unscale_ (aten/src/ATen/native/cuda/
+ * AmpKernels.cu) over n <= 48 fp32 gradient tensors in one launch:
+ * g *= *inv_scale, and *found_inf = 1 if any element is inf or NaN
+ * (found_inf is never cleared here). */
+int dgx_amp_unscale_f32(int n, float* const* grads, const int64_t* numels, const float* inv_scale, float* found_inf,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
