@@ -21,6 +21,8 @@
 //   dgcnn                                 DGCNN.forward as one op with a C++ autograd node
 //                                         (eager training: ~60 launches without a Python frame)
 //   knn_timing                            per-thread HIP-event timing of the kNN selection launches
+//   layout                                the name tables of the saved-state lists and the opts word
+//                                         (dgx.schedule names the same fields: one layout, checked by a test)
 #include <ATen/ATen.h>
 #include <ATen/core/dispatch/Dispatcher.h>
 #include <torch/library.h>
@@ -58,28 +60,25 @@ T* P(const Tensor& t) { return t.defined() && t.numel() ? static_cast<T*>(t.data
 
 int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// A/B switches of the schedule (dgx.edgeconv / dgx.gemm environment flags), one word
-struct Opts {
-  bool packed = true;        // bf16 / split fp32: backward scatter reads packed dz|slot words
-  bool fold_bwd = true;      // BN backward finalize in the scatter's prologue
-  bool fuse_image = true;    // blocks' apply writes the next kNN's operand image
-  bool fuse_edge_dz = true;  // bf16: block l-1's dz from block l's dX GEMM epilogue
-  int64_t slab_cap_mb = 8;   // split-K slab cap of small weight gradients (0 = off)
-  bool split32 = true;       // fp32 mode: conv5 GEMMs as 3-pass split bf16 (hi.hi + hi.lo + lo.hi)
-  bool push = false;         // backward scatter: selected-edge dz pushed from the sources (fixed-point LDS sums)
-  bool split_edge = false;   // fp32 mode: EdgeConv dW / dX as 3-pass split bf16 on the scatter's split dPQ planes
+// A/B switches of the schedule (dgx.edgeconv / dgx.gemm environment flags), one word:
+// bit i is switch kOptNames[i] (dgx.schedule.OPT_BITS), bits 8-15 the slab cap
+enum OptBit { kScatterPacked, kFoldBnBwd, kFuseKnnImage, kFuseEdgeDz, kSplit32, kScatterPush, kSplit32Edge, kNumOptBits };
+const char* const kOptNames[kNumOptBits] = {"SCATTER_PACKED", "FOLD_BN_BWD", "FUSE_KNN_IMAGE", "FUSE_EDGE_DZ",
+                                            "SPLIT32",        "SCATTER_PUSH", "SPLIT32_EDGE"};
+struct Opts {                // one member per OptBit, in that order, then the slab cap
+  bool packed;               // bf16 / split fp32: backward scatter reads packed dz|slot words
+  bool fold_bwd;             // BN backward finalize in the scatter's prologue
+  bool fuse_image;           // blocks' apply writes the next kNN's operand image
+  bool fuse_edge_dz;         // bf16: block l-1's dz from block l's dX GEMM epilogue
+  bool split32;              // fp32 mode: conv5 GEMMs as 3-pass split bf16 (hi.hi + hi.lo + lo.hi)
+  bool push;                 // backward scatter: selected-edge dz pushed from the sources (fixed-point LDS sums)
+  bool split_edge;           // with split32: EdgeConv dW / dX as 3-pass split bf16 on the scatter's split dPQ planes
+  int64_t slab_cap_mb;       // split-K slab cap of small weight gradients (0 = off)
 };
 Opts decode(int64_t o) {
-  Opts r;
-  r.packed = o & 1;
-  r.fold_bwd = o & 2;
-  r.fuse_image = o & 4;
-  r.fuse_edge_dz = o & 8;
-  r.slab_cap_mb = (o >> 8) & 0xff;
-  r.split32 = o & 16;
-  r.push = o & 32;
-  r.split_edge = o & 64;
-  return r;
+  auto bit = [o](OptBit b) { return ((o >> b) & 1) != 0; };
+  return Opts{bit(kScatterPacked), bit(kFoldBnBwd),  bit(kFuseKnnImage), bit(kFuseEdgeDz), bit(kSplit32),
+              bit(kScatterPush),   bit(kSplit32Edge), (o >> 8) & 0xff};
 }
 
 struct Dev {
@@ -685,7 +684,10 @@ std::vector<Tensor> stack_weights_f32(const Dev& d, const std::vector<Layer>& L,
   return out;
 }
 
-constexpr int kPerLayer = 9;   // saved per block: idx, PQ, ysel, arg, sumP, scale, shift, mean, invstd
+// a chain's saved list: x_pm, then per block these fields (dgx.schedule.CHAIN_FIELDS)
+enum ChainField { kIdx, kPQ, kYsel, kArg, kSumP, kScale, kShift, kMean, kInvstd, kPerLayer };
+const char* const kChainNames[kPerLayer] = {"idx", "PQ", "ysel", "arg", "sumP", "scale", "shift", "mean", "invstd"};
+const Tensor& field(const std::vector<Tensor>& saved, int l, ChainField f) { return saved[1 + kPerLayer * l + f]; }
 
 struct ChainOut {
   Tensor xcat, xcat16, prep;        // xcat16 / prep empty when not made
@@ -763,7 +765,6 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
       idx = knn32(d, xv, k, DGX_ORDER_STRIDED, have_prepared ? &next_prepared : nullptr);
     }
     have_prepared = false;
-    bool used_prep = false;
     if (cin <= kSmallKMax) {
       // raw coordinates (block 1, K = 3): exact fp32 in every mode, the reference weight layout read as is
       Tensor wr = ly.w.reshape({co, 2 * cin}).contiguous();
@@ -775,7 +776,6 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
       Tensor X16 = li > 0 ? xcat16.narrow(1, off_in, cin) : Tensor();
       if (have16 && block_uses_prep(bf16, li, prev_selecting, cin, total, off_in) && lds_ok(X16, cin) &&
           (int)preps.size() >= li) {
-        used_prep = true;
         PQ = lds_xwt(d, X16, preps[li - 1].first, nullptr, false);   // split weight [hi | lo]: 16 significant bits
       } else {
         PQ = mm_xwt(d, X, split_weight(ly.w, cin, co), nullptr);   // fp32 operands rounded while staged
@@ -783,8 +783,6 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
     } else {
       PQ = mm32(d, X, w32[li].t(), nullptr, false);
     }
-    (void)used_prep;
-    Tensor out_view = r.xcat.narrow(1, off, co);
     float* out = P(r.xcat) + off;
     void* out16 = bf16 ? static_cast<void*>(static_cast<at::BFloat16*>(xcat16.data_ptr()) + off) : nullptr;
     const bool use_batch = ly.bn.use_batch();
@@ -812,7 +810,7 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
       }
       have16 = bf16;
       prev_selecting = true;
-      r.saved.insert(r.saved.end(), {idx, PQ, ysel, arg, sumP, st.scale, st.shift, st.mean, st.invstd});
+      r.saved.insert(r.saved.end(), {idx, PQ, ysel, arg, sumP, st.scale, st.shift, st.mean, st.invstd});   // ChainField order
       r.stats.push_back(st);
     } else {   // inference with running statistics: one fused select + affine + LReLU pass
       Stats st = running_stats(d, ly.gamma, ly.beta, ly.bn);
@@ -824,7 +822,6 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
       for (int j = 0; j < kPerLayer; ++j) r.saved.push_back(at::empty({0}, d.f32));
       r.stats.push_back(st);
     }
-    (void)out_view;
     off_in = off;
     off += co;
   }
@@ -871,9 +868,9 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
   std::vector<const int32_t*> ids;
   std::vector<Tensor> rowptr(n), edges(n);
   for (int li = 0; li < n; ++li) {
-    selecting[li] = saved[1 + kPerLayer * li].numel() > 0;
+    const Tensor& idx = field(saved, li, kIdx);
+    selecting[li] = idx.numel() > 0;
     TORCH_CHECK(selecting[li], "dgx chain backward: block ", li + 1, " ran without its backward state");
-    const Tensor& idx = saved[1 + kPerLayer * li];
     TORCH_CHECK(idx.scalar_type() == at::kInt && idx.is_contiguous(), "dgx: kNN ids must be contiguous int32");
   }
   // reverse kNN graphs of every block in one launch (<= 8 per launch)
@@ -884,7 +881,7 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
     for (int j = 0; j < m; ++j) {
       rowptr[base + j] = at::empty({M + 1}, d.i32);
       edges[base + j] = at::empty({M * k}, d.i32);
-      ip[j] = P<int32_t>(saved[1 + kPerLayer * (base + j)]);
+      ip[j] = P<int32_t>(field(saved, base + j, kIdx));
       rp[j] = P<int32_t>(rowptr[base + j]);
       ep[j] = P<int32_t>(edges[base + j]);
     }
@@ -930,8 +927,8 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
     const int cin = ly.cin, co = ly.co;
     off -= co;
     const int64_t prev = li > 0 ? off - L[li - 1].co : 0;
-    const Tensor* s = &saved[1 + kPerLayer * li];
-    const Tensor &PQ = s[1], &ysel = s[2], &arg = s[3], &sumP = s[4];
+    const Tensor &idx = field(saved, li, kIdx), &PQ = field(saved, li, kPQ), &ysel = field(saved, li, kYsel),
+                 &arg = field(saved, li, kArg), &sumP = field(saved, li, kSumP);
     const Stats& st = stats[li];
     const Tensor X = li == 0 ? x_pm : xcat.narrow(1, prev, cin);
     const bool uses_prep = block_uses_prep(bf16, li, li > 0 && selecting[li - 1], cin, total, prev) &&
@@ -976,22 +973,20 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
     Tensor dPQ = es ? dPQs[0] : at::empty({M, 2 * co}, bf16 ? d.bf16 : d.f32);
     Tensor dgamma, dbeta, c0, c1;
     const bool fold = st.group.empty() && o.fold_bwd;
-    if (fold && o.push) {   // BN backward finalize in the push scatter's prologue (one launch)
+    if (fold) {
       dgamma = at::empty({co}, d.f32);
       dbeta = at::empty({co}, d.f32);
       c0 = at::empty({co}, d.f32);
       c1 = at::empty({co}, d.f32);
-      check(dgx_edge_bwd_scatter_push_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(s[0]), P<int32_t>(rowptr[li]),
+    }
+    if (fold && o.push) {   // BN backward finalize in the push scatter's prologue (one launch)
+      check(dgx_edge_bwd_scatter_push_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(idx), P<int32_t>(rowptr[li]),
                                           P<int32_t>(edges[li]), P(dz), packed ? nullptr : P<uint8_t>(arg), P(sumP),
                                           B, N, k, co, P(partials), nblk, count, P(st.scale), P(st.mean),
                                           P(st.invstd), (int)st.eval, P(dgamma), P(dbeta), P(c0), P(c1),
                                           dPQ.data_ptr(), out_mode, (int)packed, d.stream),
             "edge bwd scatter");
     } else if (fold) {   // BN backward finalize in the scatter's prologue (one launch)
-      dgamma = at::empty({co}, d.f32);
-      dbeta = at::empty({co}, d.f32);
-      c0 = at::empty({co}, d.f32);
-      c1 = at::empty({co}, d.f32);
       check(dgx_edge_bwd_scatter_fin_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(rowptr[li]), P<int32_t>(edges[li]), P(dz),
                                          packed ? nullptr : P<uint8_t>(arg), P(sumP), B, N, k, co, P(partials), nblk,
                                          count, P(st.scale), P(st.mean), P(st.invstd), (int)st.eval, P(dgamma), P(dbeta),
@@ -1004,7 +999,7 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
       c0 = r[2];
       c1 = r[3];
       if (o.push)
-        check(dgx_edge_bwd_scatter_push_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(s[0]), P<int32_t>(rowptr[li]),
+        check(dgx_edge_bwd_scatter_push_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(idx), P<int32_t>(rowptr[li]),
                                             P<int32_t>(edges[li]), P(dz), packed ? nullptr : P<uint8_t>(arg), P(sumP),
                                             B, N, k, co, nullptr, 0, 0.0, P(st.scale), nullptr, nullptr, 0, nullptr,
                                             nullptr, P(c0), P(c1), dPQ.data_ptr(), out_mode, (int)packed, d.stream),
@@ -1034,14 +1029,14 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
         Tensor add = dxcat.narrow(1, prev, cin);
         if (uses_prep && o.fuse_edge_dz && packed && selecting[li - 1] && edge_dz_ok(dPQ, cin)) {
           // block li-1's dY = add + dPQ [W1;W2]: its LeakyReLU' + packed dz + BN partials in the epilogue
-          const Tensor* sp = &saved[1 + kPerLayer * (li - 1)];
           const Stats& stp = stats[li - 1];
           const Tensor& w16 = preps[li - 1].second;   // (cin, 2co)
           const int rows = dgx_gemm_edge_dz_rows((int)M, cin);
           pre_dz = at::empty({M, cin}, d.f32);
           pre_part = at::empty({rows, 2, cin}, d.f32);
           check(dgx_gemm_edge_dz_bf16(dPQ.data_ptr(), ld16(dPQ), w16.data_ptr(), ld16(w16), (int)M, cin, 2 * co,
-                                      P(add), add.stride(0), P(sp[2]), P<uint8_t>(sp[3]), P(stp.scale), P(stp.shift),
+                                      P(add), add.stride(0), P(field(saved, li - 1, kYsel)),
+                                      P<uint8_t>(field(saved, li - 1, kArg)), P(stp.scale), P(stp.shift),
                                       P(stp.mean), P(stp.invstd), (float)L[li - 1].slope, P(pre_dz), P(pre_part), rows,
                                       d.stream),
                 "gemm edge dz");
@@ -1093,6 +1088,9 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
 }
 
 // ---------------------------------------------------------------- conv5 ----
+enum PcField { kXop, kZ, kPcScale, kPcShift, kPcMean, kPcInvstd, kNt, kTn, kXhi, kXlo, kNumPcFields };
+const char* const kPcNames[kNumPcFields] = {"Xop", "Z", "scale", "shift", "mean", "invstd", "nt", "tn", "xhi", "xlo"};
+
 struct PcState {
   Tensor Xop, W, Z, nt, tn;
   Tensor xhi, xlo;   // fp32 mode, 3-pass split bf16: X's planes (nt / tn then hold [hi | lo] weights)
@@ -1100,6 +1098,31 @@ struct PcState {
   bool bf16 = false;
   int B = 0, N = 0;
   double slope = 0.2;
+
+  // the saved list of conv5 (dgx.schedule.PC_FIELDS): undefined tensors travel as empty ones
+  std::vector<Tensor> pack(const Dev& d) const {
+    auto e16 = [&](const Tensor& t) { return t.defined() ? t : at::empty({0}, d.bf16); };
+    return {Xop, Z, st.scale, st.shift, st.mean, st.invstd, e16(nt), e16(tn), e16(xhi), e16(xlo)};
+  }
+  // ... and back, from s[0 .. kNumPcFields) (weight: conv5's, any trailing 1x1 dims)
+  static PcState unpack(const Tensor* s, const std::string& group, bool eval, const Tensor& weight, bool bf16, int B,
+                        int N, double slope) {
+    auto opt = [](const Tensor& t) { return t.numel() ? t : Tensor(); };
+    PcState r;
+    r.Xop = s[kXop];
+    r.Z = s[kZ];
+    r.st = Stats{s[kPcScale], s[kPcShift], s[kPcMean], s[kPcInvstd], group, eval};
+    r.nt = opt(s[kNt]);
+    r.tn = opt(s[kTn]);
+    r.xhi = opt(s[kXhi]);
+    r.xlo = opt(s[kXlo]);
+    r.W = weight.reshape({weight.size(0), r.Xop.size(1)});
+    r.bf16 = bf16;
+    r.B = B;
+    r.N = N;
+    r.slope = slope;
+    return r;
+  }
 };
 
 // conv5 -> BN -> LeakyReLU on the point-major concat buffer (dgx.pointconv, dgcnn.py:100-102):
@@ -1247,6 +1270,16 @@ std::array<Tensor, 4> pointconv_backward_impl(const Dev& d, Tensor dout, const P
 }
 
 // ------------------------------------------------------------------- ops ----
+// a block as the backward needs it: weight, widths, slope (make_layers adds the forward's BN fields)
+Layer weight_layer(const Tensor& w, double slope) {
+  Layer ly;
+  ly.w = w;
+  ly.slope = slope;
+  ly.co = (int)w.size(0);
+  ly.cin = (int)(w.size(1) / 2);
+  return ly;
+}
+
 std::vector<Layer> make_layers(const std::vector<Tensor>& weights, const std::vector<Tensor>& gammas,
                                const std::vector<Tensor>& betas, std::vector<BnSpec> bns,
                                const std::vector<double>& slopes) {
@@ -1257,13 +1290,10 @@ std::vector<Layer> make_layers(const std::vector<Tensor>& weights, const std::ve
   for (int l = 0; l < n; ++l) {
     const Tensor& w = weights[l];
     TORCH_CHECK(w.scalar_type() == at::kFloat && w.is_cuda(), "dgx: fp32 device conv weights expected");
-    L[l].w = w;
+    L[l] = weight_layer(w, slopes[l]);
     L[l].gamma = gammas[l];
     L[l].beta = betas[l];
     L[l].bn = std::move(bns[l]);
-    L[l].slope = slopes[l];
-    L[l].co = (int)w.size(0);
-    L[l].cin = (int)(w.size(1) / 2);
   }
   return L;
 }
@@ -1271,10 +1301,9 @@ std::vector<Layer> make_layers(const std::vector<Tensor>& weights, const std::ve
 std::vector<Stats> stats_from_saved(const std::vector<Tensor>& saved, int n, const std::vector<int64_t>& eval,
                                     const std::vector<std::string>& groups) {
   std::vector<Stats> st(n);
-  for (int l = 0; l < n; ++l) {
-    const Tensor* s = &saved[1 + kPerLayer * l];
-    st[l] = Stats{s[5], s[6], s[7], s[8], groups[l], eval[l] != 0};
-  }
+  for (int l = 0; l < n; ++l)
+    st[l] = Stats{field(saved, l, kScale), field(saved, l, kShift), field(saved, l, kMean), field(saved, l, kInvstd),
+                  groups[l], eval[l] != 0};
   return st;
 }
 
@@ -1310,12 +1339,7 @@ std::tuple<Tensor, std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>
   TORCH_CHECK((int)saved.size() == 1 + kPerLayer * n && (int)eval.size() == n && (int)groups.size() == n,
               "dgx chain backward: saved state does not match the layer count");
   std::vector<Layer> L(n);
-  for (int l = 0; l < n; ++l) {
-    L[l].w = weights[l];
-    L[l].co = (int)weights[l].size(0);
-    L[l].cin = (int)(weights[l].size(1) / 2);
-    L[l].slope = slopes[l];
-  }
+  for (int l = 0; l < n; ++l) L[l] = weight_layer(weights[l], slopes[l]);
   Tensor pbuf = defined_or_none(prep);
   std::vector<std::pair<Tensor, Tensor>> views;
   if (pbuf.defined()) views = prep_views(pbuf, chain_prep_jobs(L));
@@ -1328,7 +1352,7 @@ std::tuple<Tensor, std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>
   return {g.dx, g.dw, g.dgamma, g.dbeta};
 }
 
-// dgx_host::pointconv_forward -> (out, [Xop, Z, scale, shift, mean, invstd, nt, tn, xhi, xlo])
+// dgx_host::pointconv_forward -> (out, PcState::pack)
 std::tuple<Tensor, std::vector<Tensor>> pointconv_forward(
     const Tensor& X, const Tensor& X16, int64_t B, int64_t N, const Tensor& weight, const Tensor& gamma,
     const Tensor& beta, const c10::List<std::optional<Tensor>>& bn_t_l, std::vector<double> bn_f,
@@ -1346,9 +1370,7 @@ std::tuple<Tensor, std::vector<Tensor>> pointconv_forward(
   PcState s;
   Tensor out = pointconv_forward_impl(d, X, X16, (int)B, (int)N, ly, bf16, defined_or_none(nt), defined_or_none(tn), &s,
                                       decode(opts).split32);
-  auto e16 = [&](const Tensor& t) { return t.defined() ? t : at::empty({0}, d.bf16); };
-  return {out, {s.Xop, s.Z, s.st.scale, s.st.shift, s.st.mean, s.st.invstd, e16(s.nt), e16(s.tn), e16(s.xhi),
-                e16(s.xlo)}};
+  return {out, s.pack(d)};
 }
 
 // dgx_host::pointconv_backward -> (dX, dW, dgamma, dbeta). The fp32 mode's split
@@ -1357,19 +1379,11 @@ std::tuple<Tensor, std::vector<Tensor>> pointconv_forward(
 std::tuple<Tensor, Tensor, Tensor, Tensor> pointconv_backward(const Tensor& dout, std::vector<Tensor> saved,
                                                               const Tensor& weight, int64_t B, int64_t N, double slope,
                                                               bool eval, std::string group, bool bf16, int64_t opts) {
-  TORCH_CHECK(saved.size() == 10, "dgx pointconv backward: 10 saved tensors expected");
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(saved[1].device());
-  Dev d(saved[1]);
-  PcState s;
-  s.Xop = saved[0];
-  s.Z = saved[1];
-  s.st = Stats{saved[2], saved[3], saved[4], saved[5], group, eval};
-  s.nt = saved[6].numel() ? saved[6] : Tensor();
-  s.tn = saved[7].numel() ? saved[7] : Tensor();
-  s.xhi = saved[8].numel() ? saved[8] : Tensor();
-  s.xlo = saved[9].numel() ? saved[9] : Tensor();
+  TORCH_CHECK(saved.size() == kNumPcFields, "dgx pointconv backward: ", (int)kNumPcFields, " saved tensors expected");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(saved[kZ].device());
+  Dev d(saved[kZ]);
+  PcState s = PcState::unpack(saved.data(), group, eval, weight, bf16, (int)B, (int)N, slope);
   const int64_t K = s.Xop.size(1), Co = weight.size(0);
-  s.W = weight.reshape({Co, K});
   if (!bf16 && !s.xhi.defined() && decode(opts).split32 && s.Xop.scalar_type() == at::kFloat && K % 64 == 0 &&
       Co % 64 == 0) {
     auto xs = split16(d, s.Xop);
@@ -1379,10 +1393,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pointconv_backward(const Tensor& dout
     s.nt = pw.second[0].first;
     s.tn = pw.second[0].second;
   }
-  s.bf16 = bf16;
-  s.B = (int)B;
-  s.N = (int)N;
-  s.slope = slope;
   SlabJobs slabs;
   auto r = pointconv_backward_impl(d, dout, s, &slabs);
   slabs.flush(d.stream);
@@ -1447,9 +1457,7 @@ DgcnnRun dgcnn_run(const Dev& d, const Tensor& x, std::vector<Layer>& all, const
   std::vector<std::pair<Tensor, Tensor>> views;
   Tensor pbuf;
   std::vector<PrepJob> jobs;
-  const bool want_prep = c.bf16;
-  (void)need_grad;
-  if (want_prep) {
+  if (c.bf16) {
     jobs = chain_prep_jobs(blocks);
     jobs.push_back({c5.w.reshape({c5.w.size(0), c5.w.size(1)}), (int)c5.w.size(0), (int)c5.w.size(1), false, false});
     auto pw = prep_weights(d, jobs);
@@ -1458,10 +1466,10 @@ DgcnnRun dgcnn_run(const Dev& d, const Tensor& x, std::vector<Layer>& all, const
   }
   DgcnnRun r;
   const Opts o = decode(c.opts);
-  r.chain = chain_forward_impl(d, x, (int)c.k, blocks, c.bf16, need_grad, want_prep ? &views : nullptr, idx0, o);
-  r.chain.prep = want_prep ? pbuf : Tensor();
+  r.chain = chain_forward_impl(d, x, (int)c.k, blocks, c.bf16, need_grad, c.bf16 ? &views : nullptr, idx0, o);
+  r.chain.prep = pbuf;
   Tensor nt5, tn5;
-  if (want_prep) {   // conv5's copies: the job after the blocks'
+  if (c.bf16) {   // conv5's copies: the job after the blocks'
     nt5 = views[L - 2].first;
     tn5 = views[L - 2].second;
   }
@@ -1488,9 +1496,8 @@ class DgcnnFn : public torch::autograd::Function<DgcnnFn> {
     state.push_back(r.chain.xcat);
     state.push_back(r.chain.xcat16);
     state.push_back(r.chain.prep.defined() ? r.chain.prep : at::empty({0}, d.bf16));
-    auto e16 = [&](const Tensor& t) { return t.defined() ? t : at::empty({0}, d.bf16); };
-    state.insert(state.end(), {r.pc.Xop, r.pc.Z, r.pc.st.scale, r.pc.st.shift, r.pc.st.mean, r.pc.st.invstd,
-                               e16(r.pc.nt), e16(r.pc.tn), e16(r.pc.xhi), e16(r.pc.xlo)});
+    auto pcs = r.pc.pack(d);
+    state.insert(state.end(), pcs.begin(), pcs.end());
     ctx->saved_data["state"] = at::IValue(c10::List<Tensor>(state));
     ctx->saved_data["k"] = c.k;
     ctx->saved_data["bf16"] = c.bf16;
@@ -1527,27 +1534,11 @@ class DgcnnFn : public torch::autograd::Function<DgcnnFn> {
     const size_t nsaved = 1 + kPerLayer * n;
     std::vector<Tensor> saved(S.begin(), S.begin() + nsaved);
     const Tensor &xcat = S[nsaved], &xcat16 = S[nsaved + 1], &pbuf = S[nsaved + 2];
-    PcState pc;
-    pc.Xop = S[nsaved + 3];
-    pc.Z = S[nsaved + 4];
-    pc.st = Stats{S[nsaved + 5], S[nsaved + 6], S[nsaved + 7], S[nsaved + 8], groups[n], eval[n] != 0};
-    pc.nt = S[nsaved + 9].numel() ? S[nsaved + 9] : Tensor();
-    pc.tn = S[nsaved + 10].numel() ? S[nsaved + 10] : Tensor();
-    pc.xhi = S[nsaved + 11].numel() ? S[nsaved + 11] : Tensor();
-    pc.xlo = S[nsaved + 12].numel() ? S[nsaved + 12] : Tensor();
+    TORCH_CHECK(S.size() == nsaved + 3 + kNumPcFields, "dgx dgcnn backward: saved state does not match the layer count");
     const Tensor& w5 = params[3 * n];
-    pc.W = w5.reshape({w5.size(0), pc.Xop.size(1)});
-    pc.bf16 = bf16;
-    pc.B = B;
-    pc.N = N;
-    pc.slope = bn_f[3 * n + 2];
+    PcState pc = PcState::unpack(&S[nsaved + 3], groups[n], eval[n] != 0, w5, bf16, B, N, bn_f[3 * n + 2]);
     std::vector<Layer> blocks(n);
-    for (int l = 0; l < n; ++l) {
-      blocks[l].w = params[3 * l];
-      blocks[l].co = (int)params[3 * l].size(0);
-      blocks[l].cin = (int)(params[3 * l].size(1) / 2);
-      blocks[l].slope = bn_f[3 * l + 2];
-    }
+    for (int l = 0; l < n; ++l) blocks[l] = weight_layer(params[3 * l], bn_f[3 * l + 2]);
     std::vector<std::pair<Tensor, Tensor>> views;
     if (pbuf.numel()) views = prep_views(pbuf, chain_prep_jobs(blocks));
     auto st = stats_from_saved(saved, n, eval, groups);
@@ -1614,6 +1605,11 @@ std::vector<double> knn_timing(bool on) {
   return out;
 }
 
+// dgx_host::layout(): this file's name tables (dgx.schedule holds the same ones; a test compares them)
+std::tuple<std::vector<std::string>, std::vector<std::string>, std::vector<std::string>> layout() {
+  return {{kChainNames, kChainNames + kPerLayer}, {kPcNames, kPcNames + kNumPcFields}, {kOptNames, kOptNames + kNumOptBits}};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dgx_host, m) {
@@ -1631,6 +1627,7 @@ TORCH_LIBRARY(dgx_host, m) {
   m.def("dgcnn(Tensor x, Tensor[] params, Tensor?[] bufs, float[] bn_f, int[] bn_i, str[] groups, Tensor? idx0, "
         "int k, bool bf16, int opts) -> Tensor");
   m.def("knn_timing(bool on) -> float[]", &knn_timing);
+  m.def("layout() -> (str[] chain_fields, str[] pointconv_fields, str[] opts_bits)", &layout);
 }
 
 TORCH_LIBRARY_IMPL(dgx_host, CompositeImplicitAutograd, m) {

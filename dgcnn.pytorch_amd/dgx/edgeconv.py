@@ -7,7 +7,7 @@ and then cat(x1..x4) (dgcnn.py:100).
 
 Engine: one autograd node for the whole chain, whose schedule is the C++ one
 (csrc/dgx_torch.cpp: dgx_host::chain_forward / chain_backward, shared with the
-eager DGCNN op and the torch.library ops). Activations live point-major in
+eager DGCNN op and the torch.library ops; called through dgx.schedule). Activations live point-major in
 ONE concat buffer xcat (B*N, sum Co) in HBM; block l reads its input as a
 column slice of xcat and writes its output straight into its own slice, so the
 torch.cat of dgcnn.py:100 is free. Per block:
@@ -22,6 +22,10 @@ Backward per block (reverse order):
 BatchNorm decisions follow each BN module's own flags (dgx.bn). Under
 fp16/bf16 torch.autocast the chain's GEMMs take the bf16 path
 (precision.effective); kNN, BN and the elementwise work stay fp32.
+
+The A/B switches below are the bits of the schedule's ``opts`` word
+(schedule.OPT_BITS; ``opts`` reads them when it is called, so a tool may set
+``dgx.edgeconv.NAME`` at run time).
 """
 import ctypes
 import os
@@ -30,12 +34,10 @@ import threading
 import torch
 
 from . import _native as nat
-from . import bn as bn_
 from . import cpu
-from . import gemm as G
 from . import precision as prec
-from . import ops as _ops
-from .ops import knn_raw, reduction_order
+from . import schedule as S
+from .schedule import opts  # noqa: F401  (documented here: dgx.edgeconv.opts)
 
 _tls = threading.local()
 
@@ -105,13 +107,6 @@ def _reverse_graphs(idxs, B, N, k, dev):
     return list(zip(rowptrs, edges))
 
 
-class _Layer:
-    """Non-tensor description of one block (weights are passed as tensors)."""
-
-    def __init__(self, cin, cout, bn, slope):
-        self.cin, self.cout, self.bn, self.slope = cin, cout, bn, slope
-
-
 def split_weight(w, cin, cout):
     """Reference conv weight (Co, 2C[,1,1]) = [W1 | W2] -> stacked [W1; W2] (2Co, C):
     rows [0,Co) produce P (neighbour half, channels [0,C)), rows [Co,2Co) Q (centre half)."""
@@ -136,48 +131,17 @@ def edge_select(PQ, idx, B, N, k, co, gamma, stream):
     return ysel, arg, sumP, partials, prow
 
 
-def opts(split=None):
-    """The A/B switches above and gemm.SLAB_CAP_MB as the C++ schedule's
-    ``opts`` word (csrc/dgx_torch.cpp ``decode``). ``split``: whether the op's
-    fp32 GEMMs run as split bf16 — decided at the op's entry
-    (``precision.split()``, which sees autocast); None = the global mode's."""
-    if split is None:
-        split = prec.get() == "fp32_split"
-    split = bool(split or SPLIT32)
-    cap = max(0, min(255, int(G.SLAB_CAP_MB)))
-    return (int(SCATTER_PACKED) | 2 * int(FOLD_BN_BWD) | 4 * int(FUSE_KNN_IMAGE) | 8 * int(FUSE_EDGE_DZ)
-            | 16 * int(split) | 32 * int(SCATTER_PUSH) | 64 * int(split and SPLIT32_EDGE) | (cap << 8))
-
-
-PER_LAYER = 9   # saved per block: idx, PQ, ysel, arg, sumP, scale, shift, mean, invstd
-
-
-def _bn_lists(layers):
-    bn_t, bn_f, bn_i, groups, slopes = [], [], [], [], []
-    for ly in layers:
-        t, f, i, g = bn_.op_args(ly.bn)
-        bn_t += t
-        bn_f += f + [float(ly.slope)]
-        bn_i += i
-        groups.append(g)
-        slopes.append(float(ly.slope))
-    return bn_t, bn_f, bn_i, groups, slopes
-
-
 def capture_decisions(dbg, saved, xcat, xcat16):
     """Debug capture of one chain forward from its saved state: per selecting
     block ("fwd", l) = (idx, max/min slot, LeakyReLU sign), plus the blocks'
     inputs (tests re-derive each block's kNN and decisions from them)."""
-    n = (len(saved) - 1) // PER_LAYER
-    for li in range(n):
-        t = saved[1 + PER_LAYER * li: 1 + PER_LAYER * (li + 1)]
-        if t[0].numel() == 0:
+    for li, b in enumerate(S.chain_blocks(saved)):
+        if b.idx.numel() == 0:
             continue
-        idx, ysel, arg, scale, shift = t[0], t[2], t[3], t[5], t[6]
         # sign of fmaf(scale, ysel, shift) as the kernels evaluate it: the fp64
         # product of two fp32 values is exact, so this sign is fma's sign
-        zpos = (scale.double() * ysel.double() + shift.double()) > 0
-        dbg[("fwd", li)] = (idx.clone(), arg.clone(), zpos)
+        zpos = (b.scale.double() * b.ysel.double() + b.shift.double()) > 0
+        dbg[("fwd", li)] = (b.idx.clone(), b.arg.clone(), zpos)
     dbg["xcat"] = xcat
     dbg["xcat16"] = xcat16 if xcat16.numel() else None
 
@@ -189,20 +153,14 @@ class _EdgeConvStack(torch.autograd.Function):
 
     @staticmethod
     @prec.no_autocast
-    def forward(ctx, x, k, layers, prep, idx0, bf16, op_opts, need_grad, *params):
-        from . import host
-        host.load()
+    def forward(ctx, x, k, bn, prep, idx0, d, need_grad, *params):
         x = x.float()
         weights, gammas, betas = list(params[0::3]), list(params[1::3]), list(params[2::3])
-        bn_t, bn_f, bn_i, groups, slopes = _bn_lists(layers)
-        xcat, xcat16, saved, prep_out = torch.ops.dgx_host.chain_forward(
-            x, k, weights, gammas, betas, bn_t, bn_f, bn_i, groups, slopes, bool(bf16), bool(need_grad), prep, idx0,
-            op_opts)
+        xcat, xcat16, saved, prep_out = S.chain_forward(x, k, weights, gammas, betas, bn, d, need_grad, prep, idx0)
         dbg = debug_capture()
         if dbg is not None:
             capture_decisions(dbg, saved, xcat, xcat16)
-        ctx.meta = (k, tuple(x.shape), bool(bf16), [int(not bn_.mode(ly.bn)[0]) for ly in layers], groups, slopes,
-                    len(saved), op_opts)
+        ctx.meta = (k, tuple(x.shape), bn.evals, bn.groups, bn.slopes, len(saved), d)
         # x itself is saved: its version counter guards the point-major rows (a view of x)
         ctx.save_for_backward(x, xcat, xcat16, prep_out, *saved, *weights)
         ctx.mark_non_differentiable(xcat16)
@@ -212,31 +170,29 @@ class _EdgeConvStack(torch.autograd.Function):
     @staticmethod
     @prec.no_autocast
     def backward(ctx, dxcat, _unused):
-        k, shape, bf16, evals, groups, slopes, ns, op_opts = ctx.meta
+        k, shape, evals, groups, slopes, ns, d = ctx.meta
         n = len(slopes)
         if dxcat is None:
-            return (None,) * (8 + 3 * n)
+            return (None,) * (7 + 3 * n)
         t = ctx.saved_tensors
         xcat, xcat16, prep = t[1], t[2], t[3]
         saved, weights = list(t[4:4 + ns]), list(t[4 + ns:])
-        dx, dws, dgs, dbs = torch.ops.dgx_host.chain_backward(
-            dxcat, xcat, xcat16, saved, weights, prep if prep.numel() else None, list(shape), k, evals, groups, slopes,
-            bf16, ctx.needs_input_grad[0], op_opts)
+        dx, dws, dgs, dbs = S.chain_backward(dxcat, xcat, xcat16, saved, weights, prep if prep.numel() else None, shape,
+                                             k, evals, groups, slopes, d, ctx.needs_input_grad[0])
         grads = [g for trip in zip(dws, dgs, dbs) for g in trip]
-        return (dx if dx.numel() else None, None, None, None, None, None, None, None, *grads)
+        return (dx if dx.numel() else None, None, None, None, None, None, None, *grads)
 
 
-def _layers_and_params(convs, weights=None):
-    layers, params = [], []
+def _bn_and_params(convs, weights=None):
+    """(schedule.bn_lists of the blocks, their (weight, gamma, beta) triples flattened)"""
+    params, bns, slopes = [], [], []
     for li, seq in enumerate(convs):
         conv, bn, act = seq[0], seq[1], seq[2]
-        co, c2 = conv.weight.shape[0], conv.weight.shape[1]
-        if conv.bias is not None or bn.weight is None:
-            raise NotImplementedError("dgx EdgeConv expects Conv2d(bias=False) + affine BatchNorm "
-                                      "(as the reference builds them, dgcnn.py:54-73)")
-        layers.append(_Layer(c2 // 2, co, bn, act.negative_slope))
+        S.require_plain_conv_bn(conv, bn)
         params += [conv.weight if weights is None else weights[li], bn.weight, bn.bias]
-    return layers, params
+        bns.append(bn)
+        slopes.append(act.negative_slope)
+    return S.bn_lists(bns, slopes), params
 
 
 def edgeconv_stack_pair(x, k, convs, training=None, preps=None, weights=None):
@@ -256,19 +212,13 @@ def edgeconv_stack_pair(x, k, convs, training=None, preps=None, weights=None):
     nat.require_device(x)
     if x.dtype != torch.float32:
         x = x.float()
-    layers, params = _layers_and_params(convs, weights)
-    eff = prec.effective()
-    bf16 = eff == "bf16"
+    bn, params = _bn_and_params(convs, weights)
     # whether this forward will be differentiated (inside Function.forward grad
     # mode is always off, so it is decided here)
     need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-    idx0 = None
-    if getattr(_ops._tls, "cache", None) is not None:
-        # inside a kNN-sharing scope (Net.forward): block 1's kNN is the scope's entry
-        idx0 = knn_raw(x.detach(), k, order=reduction_order(x), out_dtype=torch.int32)
     if isinstance(preps, (list, tuple)):
         preps = None
-    return _EdgeConvStack.apply(x, k, layers, preps, idx0, bf16, opts(eff == "fp32_split"), need_grad, *params)
+    return _EdgeConvStack.apply(x, k, bn, preps, S.shared_idx0(x, k), S.decide(), need_grad, *params)
 
 
 def edgeconv_stack(x, k, convs, training=None):

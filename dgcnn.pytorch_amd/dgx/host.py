@@ -5,8 +5,9 @@ node, the whole backward — the ~60 launches of a step are issued from C++
 instead of one Python dispatch each.
 
 It is the same schedule the engine's autograd Functions (dgx.edgeconv,
-dgx.pointconv) and torch.library ops (dgx.library) call, one C++
-implementation for every configuration the reference's scripts run:
+dgx.pointconv) and torch.library ops (dgx.library) call — all through the one
+binding, dgx.schedule — one C++ implementation for every configuration the
+reference's scripts run:
 precision bf16, fp32 or fp32_split (bf16 autocast -> bf16 GEMMs, fp16
 autocast -> split-bf16 fp32 GEMMs, dgx.precision.effective), BatchNorm in
 training or eval mode, momentum or cumulative running statistics, plain
@@ -21,10 +22,8 @@ import threading
 
 import torch
 
-from . import bn as bn_
 from . import edgeconv as E
-from . import ops
-from . import precision as prec
+from . import schedule as S
 
 ENABLED = os.environ.get("DGX_HOST_EXT", "1") == "1"
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -57,31 +56,22 @@ def applies(model, x):
         return False
     for seq in model.edge_blocks() + [model.conv5]:
         conv, bn = seq[0], seq[1]
-        if conv.bias is not None or bn.weight is None or conv.weight.dtype != torch.float32:
+        if not S.plain_conv_bn(conv, bn) or conv.weight.dtype != torch.float32:
             return False
     return True
 
 
 def dgcnn_forward(model, x):
-    """DGCNN.forward through torch.ops.dgx_host.dgcnn."""
-    load()
-    eff = prec.effective()
-    bf16 = eff == "bf16"
+    """DGCNN.forward through the one-op schedule (dgx_host::dgcnn)."""
     if x.dtype != torch.float32:
         x = x.float()
-    params, bufs, bn_f, bn_i, groups = [], [], [], [], []
+    params, bns, slopes = [], [], []
     weights = model.edge_weights() + [model.conv5[0].weight]   # re-parameterised in edge_mode "diff"
     for w, seq in zip(weights, model.edge_blocks() + [model.conv5]):
-        bn, act = seq[1], seq[2]
+        bn, act = seq[1], seq[2]   # (one lookup each: nn.Sequential indexing is slow on this path)
         params += [w, bn.weight, bn.bias]
-        t, f, i, g = bn_.op_args(bn)
-        bufs += t[:3]          # running statistics updated in place
-        bn_f += f + [float(act.negative_slope)]
-        bn_i += i
-        groups.append(g)
-    idx0 = None
-    if getattr(ops._tls, "cache", None) is not None:
-        # inside a kNN-sharing scope (Net.forward): block 1's kNN is the scope's entry
-        idx0 = ops.knn_raw(x.detach(), model.k, order=ops.reduction_order(x), out_dtype=torch.int32)
-    return torch.ops.dgx_host.dgcnn(x, params, bufs, bn_f, bn_i, groups, idx0, model.k, bf16,
-                                    E.opts(eff == "fp32_split"))
+        bns.append(bn)
+        slopes.append(act.negative_slope)
+    # the running statistics are updated in place: the module buffers only
+    bn = S.bn_lists(bns, slopes, targets=False)
+    return S.dgcnn(x, model.k, params, bn, S.decide(), S.shared_idx0(x, model.k))

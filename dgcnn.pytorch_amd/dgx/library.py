@@ -24,8 +24,10 @@ into the outputs: no private copy first) and the caller copies them into the
 module buffers (what a compiled graph does with a buffer mutation anyway;
 torch does not allow an autograd formula on an op that mutates its inputs).
 The chain and conv5 ops run the C++ schedule (libdgx_torch.so,
-dgx_host::chain_* / pointconv_*) that the eager DGCNN op and the engine's
-autograd Functions run too, so eager results are identical either way;
+dgx_host::chain_* / pointconv_*, through dgx.schedule) that the eager DGCNN op
+and the engine's autograd Functions run too, with the precision / options
+decision of the forward's entry as an explicit ``opts`` argument that their
+backward ops get back, so eager results are identical either way;
 ``models.dgcnn.DGCNN`` takes this path while torch.compile traces it, unless a
 BatchNorm is a SyncBatchNorm (process groups cannot cross the op boundary).
 """
@@ -36,10 +38,10 @@ from torch import Tensor
 
 from . import bn as bn_
 from . import cpu
-from . import edgeconv as E
 from . import gemm as G
 from . import ops
 from . import precision as prec
+from . import schedule as S
 
 ENABLED = True
 _F32, _BF16, _I32 = torch.float32, torch.bfloat16, torch.int32
@@ -262,47 +264,38 @@ def _dgcnn_prep_shapes(weights5):
 
 
 # --------------------------------------------------------- edgeconv chain ----
-_PER_LAYER = 9   # idx, PQ, ysel, arg, sumP, scale, shift, mean, invstd
-
-
-def _chain_layers(weights, specs, slopes):
-    return [E._Layer(w.shape[1] // 2, w.shape[0], s, sl) for w, s, sl in zip(weights, specs, slopes)]
-
-
 @torch.library.custom_op("dgx::edgeconv_chain", mutates_args=(), device_types="cuda")
 def edgeconv_chain(x: Tensor, k: int, weights: list[Tensor], gammas: list[Tensor], betas: list[Tensor],
                    running_means: list[Tensor], running_vars: list[Tensor], nbts: list[Tensor], training: list[bool],
                    track: list[bool], momentum: list[float], eps: list[float], slopes: list[float], bf16: bool,
-                   need_grad: bool, prep: Optional[Tensor]) -> tuple[Tensor, Tensor, list[Tensor], list[Tensor],
-                                                                     list[Tensor], list[Tensor]]:
+                   need_grad: bool, prep: Optional[Tensor], opts: int) -> tuple[Tensor, Tensor, list[Tensor],
+                                                                                list[Tensor], list[Tensor],
+                                                                                list[Tensor]]:
     """DGCNN's EdgeConv blocks (dgcnn.py:84-100) on the C++ schedule
     (dgx_host::chain_forward): returns (concat buffer (B*N, sum Co), its bf16
     twin or empty, updated running means / vars / batch counters, the state the
     backward reads)."""
-    from . import host
-    host.load()
     outs = _stat_outputs(training, track, running_means, running_vars, nbts)
     rms, rvs, nbs = [o[0] for o in outs], [o[1] for o in outs], [o[2] for o in outs]
     specs = [_BNSpec(*a, out=o) for a, o in zip(zip(training, track, running_means, running_vars, nbts, momentum, eps),
                                                   outs)]
-    bn_t, bn_f, bn_i, groups, sl = E._bn_lists(_chain_layers(weights, specs, slopes))
-    idx0 = None
-    if getattr(ops._tls, "cache", None) is not None:
-        idx0 = ops.knn_raw(x.detach().float(), k, order=ops.reduction_order(x), out_dtype=_I32)
-    xcat, xcat16, saved, _ = torch.ops.dgx_host.chain_forward(
-        x.float(), k, weights, gammas, betas, bn_t, bn_f, bn_i, groups, sl, bf16, need_grad, prep, idx0, E.opts())
+    x32 = x.float()
+    idx0 = S.shared_idx0(x32, k)
+    xcat, xcat16, saved, _ = S.chain_forward(x32, k, weights, gammas, betas, S.bn_lists(specs, slopes),
+                                             S.Decision(bf16, opts), need_grad, prep, idx0)
     saved = list(saved)
     x_pm = saved[0]
     if x_pm.untyped_storage().data_ptr() == x.untyped_storage().data_ptr():
         saved[0] = x_pm.clone()
-    if idx0 is not None and saved[1].data_ptr() == idx0.data_ptr():
-        saved[1] = idx0.clone()   # a cache entry: never alias it
+    i0 = 1 + S.CHAIN_FIELDS.index("idx")   # block 1's kNN ids
+    if idx0 is not None and saved[i0].data_ptr() == idx0.data_ptr():
+        saved[i0] = idx0.clone()   # a cache entry: never alias it
     return xcat, xcat16, rms, rvs, nbs, saved
 
 
 @edgeconv_chain.register_fake
 def _(x, k, weights, gammas, betas, running_means, running_vars, nbts, training, track, momentum, eps, slopes,
-      bf16, need_grad, prep):
+      bf16, need_grad, prep, opts):
     B, C0, N = x.shape
     M = B * N
     widths = [w.shape[0] for w in weights]
@@ -313,11 +306,13 @@ def _(x, k, weights, gammas, betas, running_means, running_vars, nbts, training,
     saved = [x.new_empty((M, C0), dtype=_F32)]
     for li, co in enumerate(widths):
         if not selecting[li]:
-            saved += [x.new_empty((0,), dtype=_F32) for _ in range(_PER_LAYER)]
+            saved += [x.new_empty((0,), dtype=_F32) for _ in S.CHAIN_FIELDS]
             continue
-        saved += [x.new_empty((B, N, k), dtype=_I32), x.new_empty((M, 2 * co), dtype=_F32),
-                  x.new_empty((M, co), dtype=_F32), x.new_empty((M, co), dtype=torch.uint8),
-                  x.new_empty((M, co), dtype=_F32)] + [x.new_empty((co,), dtype=_F32) for _ in range(4)]
+        row, vec = x.new_empty((M, co), dtype=_F32), x.new_empty((co,), dtype=_F32)
+        saved += S.ChainBlock(idx=x.new_empty((B, N, k), dtype=_I32), PQ=x.new_empty((M, 2 * co), dtype=_F32),
+                              ysel=row, arg=x.new_empty((M, co), dtype=torch.uint8), sumP=torch.empty_like(row),
+                              scale=vec, shift=torch.empty_like(vec), mean=torch.empty_like(vec),
+                              invstd=torch.empty_like(vec))
     return (xcat, xcat16, [torch.empty_like(t) for t in running_means], [torch.empty_like(t) for t in running_vars],
             [torch.empty_like(t) for t in nbts], saved)
 
@@ -325,18 +320,17 @@ def _(x, k, weights, gammas, betas, running_means, running_vars, nbts, training,
 @torch.library.custom_op("dgx::edgeconv_chain_backward", mutates_args=(), device_types="cuda")
 def edgeconv_chain_backward(dxcat: Tensor, x: Tensor, xcat: Tensor, xcat16: Tensor, saved: list[Tensor],
                             weights: list[Tensor], gammas: list[Tensor], betas: list[Tensor], prep: Optional[Tensor],
-                            k: int, use_batch: list[bool], slopes: list[float], bf16: bool,
-                            x_needs_grad: bool) -> tuple[Tensor, list[Tensor], list[Tensor], list[Tensor]]:
-    B, C0, N = x.shape
-    dx, dws, dgs, dbs = torch.ops.dgx_host.chain_backward(
-        dxcat, xcat, xcat16, saved, weights, prep, [B, C0, N], k, [int(not u) for u in use_batch],
-        [""] * len(weights), slopes, bf16, x_needs_grad, E.opts())
+                            k: int, use_batch: list[bool], slopes: list[float], bf16: bool, x_needs_grad: bool,
+                            opts: int) -> tuple[Tensor, list[Tensor], list[Tensor], list[Tensor]]:
+    dx, dws, dgs, dbs = S.chain_backward(dxcat, xcat, xcat16, saved, weights, prep, x.shape, k,
+                                         [int(not u) for u in use_batch], [""] * len(weights), slopes,
+                                         S.Decision(bf16, opts), x_needs_grad)
     dx = dx.contiguous() if dx.numel() else _empty(x.device)
     return dx, [g.contiguous() for g in dws], list(dgs), list(dbs)
 
 
 @edgeconv_chain_backward.register_fake
-def _(dxcat, x, xcat, xcat16, saved, weights, gammas, betas, prep, k, use_batch, slopes, bf16, x_needs_grad):
+def _(dxcat, x, xcat, xcat16, saved, weights, gammas, betas, prep, k, use_batch, slopes, bf16, x_needs_grad, opts):
     dx = x.new_empty(x.shape, dtype=_F32) if x_needs_grad else x.new_empty((0,), dtype=_F32)
     return (dx, [torch.empty_like(w, dtype=_F32) for w in weights], [torch.empty_like(g, dtype=_F32) for g in gammas],
             [torch.empty_like(b, dtype=_F32) for b in betas])
@@ -344,13 +338,13 @@ def _(dxcat, x, xcat, xcat16, saved, weights, gammas, betas, prep, k, use_batch,
 
 def _chain_setup(ctx, inputs, output):
     (x, k, weights, gammas, betas, rms, rvs, nbts, training, track, momentum, eps, slopes, bf16, need_grad,
-     prep) = inputs
+     prep, opts) = inputs
     xcat, xcat16, _, _, _, saved = output
     # the running statistics and saved-state outputs take no gradient: without
     # this autograd would zero-fill one gradient per saved tensor every step
     ctx.set_materialize_grads(False)
     ctx.n, ctx.nsaved, ctx.has_prep = len(weights), len(saved), prep is not None
-    ctx.k, ctx.slopes, ctx.bf16 = k, list(slopes), bf16
+    ctx.k, ctx.slopes, ctx.bf16, ctx.opts = k, list(slopes), bf16, opts
     ctx.use_batch = [_use_batch(t, rm) for t, rm in zip(training, rms)]
     ctx.save_for_backward(x, xcat, xcat16, *saved, *weights, *gammas, *betas, *([prep] if prep is not None else []))
 
@@ -366,16 +360,21 @@ def _chain_bwd(ctx, g_xcat, _g16, _grm, _grv, _gnbt, _gsaved):
         g_xcat = torch.zeros_like(xcat)
     dx, dws, dgs, dbs = torch.ops.dgx.edgeconv_chain_backward(
         g_xcat.contiguous(), x, xcat, xcat16, saved, ws, gs, bs, prep, ctx.k, ctx.use_batch, ctx.slopes, ctx.bf16,
-        ctx.needs_input_grad[0])
+        ctx.needs_input_grad[0], ctx.opts)
     nl = [None] * n   # list-of-tensor inputs take a list of gradients (none for the BN buffers)
     return ((dx if ctx.needs_input_grad[0] else None), None, dws, dgs, dbs, nl, list(nl), list(nl), None, None, None,
-            None, None, None, None, None)
+            None, None, None, None, None, None)
 
 
 torch.library.register_autograd("dgx::edgeconv_chain", _chain_bwd, setup_context=_chain_setup)
 
 
 # -------------------------------------------------------------- pointconv ----
+# conv5's saved fields that cross the op boundary; the others alias the op's inputs (Xop: X or X16; nt / tn: views
+# of prep) or are rebuilt by the backward (xhi / xlo), so the backward op re-inserts them
+_PC_KEPT = ("Z", "scale", "shift", "mean", "invstd")
+
+
 def _pc_lds(bf16, X16, K):
     return bf16 and X16.numel() > 0 and K % 64 == 0
 
@@ -390,38 +389,36 @@ def _pc_prep(prep, Co, K):
 @torch.library.custom_op("dgx::pointconv", mutates_args=(), device_types="cuda")
 def pointconv(X: Tensor, X16: Tensor, B: int, N: int, weight: Tensor, gamma: Tensor, beta: Tensor,
               running_mean: Tensor, running_var: Tensor, nbt: Tensor, training: bool, track: bool, momentum: float,
-              eps: float, slope: float, bf16: bool, prep: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor, Tensor,
-                                                                                    list[Tensor]]:
+              eps: float, slope: float, bf16: bool, prep: Optional[Tensor],
+              opts: int) -> tuple[Tensor, Tensor, Tensor, Tensor, list[Tensor]]:
     """conv5 -> BN -> LeakyReLU on the concat buffer (dgcnn.py:100-102) on the
     C++ schedule (dgx_host::pointconv_forward): (out (B, Co, N), updated
-    running mean / var / batch counter, saved state [Z, scale, shift, mean,
-    invstd])."""
-    from . import host
-    host.load()
+    running mean / var / batch counter, saved state (_PC_KEPT))."""
     (rm, rv, nb), = _stat_outputs([training], [track], [running_mean], [running_var], [nbt])
     spec = _BNSpec(training, track, running_mean, running_var, nbt, momentum, eps, out=(rm, rv, nb))
-    t, f, i, g = bn_.op_args(spec)
     nt, tn = _pc_prep(prep, weight.shape[0], weight.shape[1])
-    out, saved = torch.ops.dgx_host.pointconv_forward(X.float(), X16, B, N, weight, gamma, beta, t, f + [float(slope)],
-                                                      i, g, bf16, nt, tn, E.opts())
-    return out, rm, rv, nb, list(saved[1:6])
+    out, saved = S.pointconv_forward(X, X16, B, N, weight, gamma, beta, S.bn_lists([spec], [slope]),
+                                     S.Decision(bf16, opts), nt, tn)
+    saved = S.PcSaved(*saved)
+    return out, rm, rv, nb, [getattr(saved, f) for f in _PC_KEPT]
 
 
 @pointconv.register_fake
 def _(X, X16, B, N, weight, gamma, beta, running_mean, running_var, nbt, training, track, momentum, eps, slope,
-      bf16, prep):
+      bf16, prep, opts):
     M, K = X.shape
     Co = weight.shape[0]
     z16 = _pc_lds(bf16, X16, K) and _use_batch(training, running_mean)
-    Z = X.new_empty((M, Co), dtype=_BF16 if z16 else _F32)
+    kept = [X.new_empty((M, Co), dtype=_BF16 if z16 else _F32) if f == "Z" else X.new_empty((Co,), dtype=_F32)
+            for f in _PC_KEPT]
     return (X.new_empty((B, Co, N), dtype=_F32), torch.empty_like(running_mean), torch.empty_like(running_var),
-            torch.empty_like(nbt), [Z] + [X.new_empty((Co,), dtype=_F32) for _ in range(4)])
+            torch.empty_like(nbt), kept)
 
 
 @torch.library.custom_op("dgx::pointconv_backward", mutates_args=(), device_types="cuda")
 def pointconv_backward(dout: Tensor, X: Tensor, X16: Tensor, weight: Tensor, saved: list[Tensor],
-                       prep: Optional[Tensor], B: int, N: int, slope: float, bf16: bool,
-                       use_batch: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+                       prep: Optional[Tensor], B: int, N: int, slope: float, bf16: bool, use_batch: bool,
+                       opts: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     M, K = X.shape
     Co = weight.shape[0]
     lds = _pc_lds(bf16, X16, K)
@@ -430,37 +427,35 @@ def pointconv_backward(dout: Tensor, X: Tensor, X16: Tensor, weight: Tensor, sav
     if lds and nt is None:
         nt, tn = G.prep_weight(weight, Co, K, False)
     # fp32 mode: the backward op rebuilds the split-bf16 planes and weights from X
-    full = [X16 if lds else X.float(), *saved, nt if lds else e16, tn if lds else e16, e16, e16]
-    dX, dW, dg, db = torch.ops.dgx_host.pointconv_backward(dout, full, weight, B, N, slope, not use_batch, "", bf16,
-                                                           E.opts())
+    full = S.PcSaved(Xop=X16 if lds else X.float(), nt=nt if lds else e16, tn=tn if lds else e16, xhi=e16, xlo=e16,
+                     **dict(zip(_PC_KEPT, saved)))
+    dX, dW, dg, db = S.pointconv_backward(dout, full, weight, B, N, slope, not use_batch, "", S.Decision(bf16, opts))
     return dX.contiguous(), dW.contiguous(), dg, db
 
 
 @pointconv_backward.register_fake
-def _(dout, X, X16, weight, saved, prep, B, N, slope, bf16, use_batch):
+def _(dout, X, X16, weight, saved, prep, B, N, slope, bf16, use_batch, opts):
     Co = weight.shape[0]
     return (X.new_empty(X.shape, dtype=_F32), torch.empty_like(weight, dtype=_F32), X.new_empty((Co,), dtype=_F32),
             X.new_empty((Co,), dtype=_F32))
 
 
 def _pc_setup(ctx, inputs, output):
-    (X, X16, B, N, weight, gamma, beta, rm, rv, nbt, training, track, momentum, eps, slope, bf16, prep) = inputs
+    (X, X16, B, N, weight, gamma, beta, rm, rv, nbt, training, track, momentum, eps, slope, bf16, prep, opts) = inputs
     ctx.set_materialize_grads(False)
-    ctx.meta = (B, N, slope, bf16, _use_batch(training, rm), prep is not None)
+    ctx.meta = (B, N, slope, bf16, _use_batch(training, rm), prep is not None, opts)
     ctx.save_for_backward(X, X16, weight, *output[4], *([prep] if prep is not None else []))
 
 
 def _pc_bwd(ctx, g_out, _grm, _grv, _gnb, _gsaved):
-    B, N, slope, bf16, use_batch, has_prep = ctx.meta
-    t = ctx.saved_tensors
-    X, X16, weight = t[0], t[1], t[2]
-    saved = list(t[3:8])
-    prep = t[8] if has_prep else None
+    B, N, slope, bf16, use_batch, has_prep, opts = ctx.meta
+    X, X16, weight, *saved = ctx.saved_tensors
+    prep = saved.pop() if has_prep else None
     if g_out is None:
         g_out = torch.zeros((B, weight.shape[0], N), dtype=torch.float32, device=X.device)
     dX, dW, dg, db = torch.ops.dgx.pointconv_backward(g_out.contiguous(), X, X16, weight, saved, prep, B, N, slope,
-                                                      bf16, use_batch)
-    return dX, None, None, None, dW, dg, db, None, None, None, None, None, None, None, None, None, None
+                                                      bf16, use_batch, opts)
+    return dX, None, None, None, dW, dg, db, None, None, None, None, None, None, None, None, None, None, None
 
 
 torch.library.register_autograd("dgx::pointconv", _pc_bwd, setup_context=_pc_setup)
@@ -503,14 +498,13 @@ def dgcnn_forward(model, x):
     B, _, N = x.shape
     x = x.float()
     dev = x.device
-    bf16 = prec.effective() == "bf16"
+    bf16, opts = S.decide()   # once, while tracing: the ops and their backwards get it as arguments
     blocks = model.edge_blocks()
     convs = [b[0] for b in blocks]
     bns = [b[1] for b in blocks]
     c5, bn5, act5 = model.conv5[0], model.conv5[1], model.conv5[2]
     for conv, bn in zip(convs + [c5], bns + [bn5]):
-        if conv.bias is not None or bn.weight is None:
-            raise NotImplementedError("dgx DGCNN expects Conv(bias=False) + affine BatchNorm (dgcnn.py:54-78)")
+        S.require_plain_conv_bn(conv, bn)
     eff = model.edge_weights()   # per-block conv weights (re-parameterised in edge_mode "diff")
     params = [p for w, bn in zip(eff + [c5.weight], bns + [bn5]) for p in (w, bn.weight, bn.bias)]
     need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
@@ -525,7 +519,7 @@ def dgcnn_forward(model, x):
         x, model.k, eff, [bn.weight for bn in bns], [bn.bias for bn in bns],
         [a[0] for a in bn_in], [a[1] for a in bn_in], [a[2] for a in bn_in], [a[3] for a in bn_in],
         [a[4] for a in bn_in], [a[5] for a in bn_in], [a[6] for a in bn_in],
-        [float(b[2].negative_slope) for b in blocks], bf16, need_grad, prep)
+        [float(b[2].negative_slope) for b in blocks], bf16, need_grad, prep, opts)
     a5 = _bn_args(bn5, dev)
     prep5 = None
     if prep is not None:
@@ -535,7 +529,7 @@ def dgcnn_forward(model, x):
         prep5 = prep[off:]
     out, rm5, rv5, nb5, _ = torch.ops.dgx.pointconv(xcat, xcat16, B, N, c5.weight, bn5.weight, bn5.bias, a5[0], a5[1],
                                                      a5[2], a5[3], a5[4], a5[5], a5[6], float(act5.negative_slope),
-                                                     bf16, prep5)
+                                                     bf16, prep5, opts)
     _store_bn(list(zip(bns, rms, rvs, nbs)) + [(bn5, rm5, rv5, nb5)])
     return out
 

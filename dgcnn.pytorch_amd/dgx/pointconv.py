@@ -16,8 +16,8 @@ import torch
 
 from . import _native as nat
 from . import cpu
-from . import bn as bn_
 from . import precision as prec
+from . import schedule as S
 
 
 class _PointConvBNLReLU(torch.autograd.Function):
@@ -27,25 +27,21 @@ class _PointConvBNLReLU(torch.autograd.Function):
 
     @staticmethod
     @prec.no_autocast
-    def forward(ctx, X, X16, B, N, bn, slope, nt, tn, bf16, op_opts, weight, gamma, beta):
-        from . import host
-        host.load()
-        t, f, i, g = bn_.op_args(bn)
+    def forward(ctx, X, X16, B, N, bn, nt, tn, d, weight, gamma, beta):
         if X16 is None:
             X16 = torch.empty(0, dtype=torch.bfloat16, device=X.device)
-        out, saved = torch.ops.dgx_host.pointconv_forward(X.float(), X16, B, N, weight, gamma, beta, t,
-                                                          f + [float(slope)], i, g, bool(bf16), nt, tn, op_opts)
-        ctx.meta = (B, N, float(slope), not bn_.mode(bn)[0], g, bool(bf16), op_opts)
+        out, saved = S.pointconv_forward(X, X16, B, N, weight, gamma, beta, bn, d, nt, tn)
+        ctx.meta = (B, N, bn.slopes[0], bn.evals[0], bn.groups[0], d)
         ctx.save_for_backward(weight, *saved)
         return out
 
     @staticmethod
     @prec.no_autocast
     def backward(ctx, dout):
-        B, N, slope, ev, g, bf16, op_opts = ctx.meta
+        B, N, slope, ev, g, d = ctx.meta
         weight, *saved = ctx.saved_tensors
-        dX, dW, dg, db = torch.ops.dgx_host.pointconv_backward(dout, saved, weight, B, N, slope, ev, g, bf16, op_opts)
-        return dX, None, None, None, None, None, None, None, None, None, dW, dg, db
+        dX, dW, dg, db = S.pointconv_backward(dout, saved, weight, B, N, slope, ev, g, d)
+        return dX, None, None, None, None, None, None, None, dW, dg, db
 
 
 def pointconv_bn_lrelu(X, B, N, seq, training=None, X16=None, wprep=None):
@@ -61,10 +57,7 @@ def pointconv_bn_lrelu(X, B, N, seq, training=None, X16=None, wprep=None):
         return cpu.pointconv_bn_lrelu(X, B, N, seq, training)
     nat.require_device(X)
     conv, bn, act = seq[0], seq[1], seq[2]
-    if conv.bias is not None or bn.weight is None:
-        raise NotImplementedError("dgx pointconv expects Conv(bias=False) + affine BatchNorm")
+    S.require_plain_conv_bn(conv, bn)
     nt, tn = wprep if wprep is not None else (None, None)
-    from .edgeconv import opts
-    eff = prec.effective()
-    return _PointConvBNLReLU.apply(X, X16, B, N, bn, act.negative_slope, nt, tn, eff == "bf16",
-                                   opts(eff == "fp32_split"), conv.weight, bn.weight, bn.bias)
+    return _PointConvBNLReLU.apply(X, X16, B, N, S.bn_lists([bn], [act.negative_slope]), nt, tn, S.decide(),
+                                   conv.weight, bn.weight, bn.bias)

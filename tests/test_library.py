@@ -93,6 +93,27 @@ def test_host_op_library_loads():
     assert not host.applies(DGCNN(types.SimpleNamespace(emb_dim=64, k=4)).train(), torch.rand(2, 3, 32))
 
 
+def test_schedule_layout_named_once(monkeypatch):
+    """The saved-state field names and the opts bits of dgx.schedule are the
+    C++ schedule's own tables (dgx_host::layout()), and ``opts()`` puts each
+    A/B switch of dgx.edgeconv at the bit of its name, read at call time."""
+    from dgx import edgeconv as E, gemm as G, host, schedule as S
+    host.load()
+    chain, pc, bits = (tuple(names) for names in torch.ops.dgx_host.layout())
+    assert (chain, pc, bits) == (S.CHAIN_FIELDS, S.PC_FIELDS, S.OPT_BITS)
+    assert E.opts is S.opts
+    monkeypatch.setattr(G, "SLAB_CAP_MB", 0)
+    for on in bits:
+        for name in bits:
+            monkeypatch.setattr(E, name, name == on)
+        assert S.opts() == 1 << bits.index(on), on
+    for name in bits:
+        monkeypatch.setattr(E, name, False)
+    assert S.opts() == 0 and S.opts(split=True) == 1 << bits.index("SPLIT32")
+    monkeypatch.setattr(G, "SLAB_CAP_MB", 8)
+    assert S.opts() == 8 << 8
+
+
 def test_knn_shape_routing():
     """Shapes outside the fused kNN kernel route to the generic path (any C,
     k up to 8192, any N) instead of failing; its workspace query is exported."""

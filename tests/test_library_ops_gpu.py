@@ -121,6 +121,48 @@ def test_torch_compile_dgcnn_fullgraph(cuda, precision):
         torch._dynamo.reset()
 
 
+def test_torch_compile_dgcnn_follows_fp16_autocast(cuda):
+    """Under fp16 autocast (main_partseg_dist.py:253) the compiled DGCNN takes
+    the decision eager takes (precision.effective: split-bf16 fp32 GEMMs), as
+    an explicit ``opts`` argument of its ops: the compiled train step equals
+    the eager one bit for bit and differs from the plain fp32 mode's."""
+    base = _model(256, 20, seed=4)
+    x = _cloud(cuda, 4, 1024, seed=9)
+    gout = torch.randn((4, 256, 1024), device=cuda)
+    me, mc, mf = (copy.deepcopy(base).to(cuda).train() for _ in range(3))
+    try:
+        compiled = torch.compile(mc, backend="aot_eager", fullgraph=True)
+        with torch.autocast("cuda", dtype=torch.float16):
+            e = _step(me, x, gout)
+            c = _step(mc, x, gout, call=compiled)
+        _assert_same(e, c)
+        assert not torch.equal(c[0], _step(mf, x, gout)[0])
+    finally:
+        torch._dynamo.reset()
+
+
+def test_op_path_decision_taken_at_forward(cuda, monkeypatch):
+    """The torch.ops.dgx path decides precision / options once, at forward
+    entry, and its backward ops get that decision back: a forward inside
+    precision "fp32_split" whose backward runs after the mode is "fp32" again
+    equals the autograd-Function path run the same way, bit for bit."""
+    from dgx import host, library, precision as prec
+    monkeypatch.setattr(host, "ENABLED", False)   # m(x) below: the Function path
+    base = _model(256, 20, seed=4)
+    x = _cloud(cuda, 4, 1024, seed=9)
+    gout = torch.randn((4, 256, 1024), device=cuda)
+
+    def step(forward):
+        m = copy.deepcopy(base).to(cuda).train()
+        with prec.mode("fp32_split"):
+            y = forward(m)
+        assert prec.get() == "fp32"
+        y.backward(gout)
+        return (y.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters()},
+                {n: b.clone() for n, b in m.named_buffers()})
+    _assert_same(step(lambda m: library.dgcnn_forward(m, x)), step(lambda m: m(x)))
+
+
 def test_torch_export_dgcnn_eval(cuda):
     """torch.export of the eval forward: one graph over the dgx ops, equal to eager."""
     import dgx.library  # noqa: F401
