@@ -131,6 +131,10 @@ _SIGS = {
     "dgx_gemm_dz2_bf16": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
     "dgx_edge_mlp_fused_fwd_bf16": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp,
                                     _vp, _i32, _vp, _vp],
+    "dgx_smoothed_ce_workspace_bytes": [_i64],
+    "dgx_smoothed_ce_fwd": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp,
+                            _sz, _vp],
+    "dgx_smoothed_ce_bwd": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "dgx_version": ctypes.c_char_p,
@@ -139,6 +143,7 @@ _RESTYPES = {
     "dgx_knn_workspace_bytes": _sz,
     "dgx_knn_image_bytes": _sz,
     "dgx_knn_generic_workspace_bytes": _sz,
+    "dgx_smoothed_ce_workspace_bytes": _sz,
 }
 
 

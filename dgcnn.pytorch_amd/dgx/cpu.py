@@ -162,6 +162,44 @@ def hog_1x1(x, idx):
     return F.normalize(hist, p=2.0, dim=2).view(B, P, -1)
 
 
+def ce_weights(dtype, n_class, smoothing=True, eps=0.2):
+    """(w_true, w_other): the two values the reference's smoothed target takes
+    (loss.py:13-14), as Python floats. The reference builds its target in the
+    logits' dtype, so its expression is evaluated here on one-element tensors of
+    that dtype at one-hot values 1 and 0; in fp16 the weights are fp16(0.8) and
+    fp16(fp16(0.2) / (C - 1)) and no longer sum to 1 over a row. Without
+    smoothing the target is the one-hot itself."""
+    if n_class < 2:
+        raise ValueError(f"dgx: a cross entropy over {n_class} class(es) has no smoothed target "
+                         "(the reference divides by n_class - 1)")
+    if not smoothing:
+        return 1.0, 0.0
+    hit = torch.tensor([1.0, 0.0], dtype=dtype)   # labelled class, any other class
+    w = hit * (1 - eps) + (1 - hit) * eps / (n_class - 1)
+    return float(w[0]), float(w[1])
+
+
+def ce_target(logits, target, smoothing=True, eps=0.2):
+    """The reference's soft target (loss.py:13-14) for (M, C) or (B, C, N)
+    logits, built from its two values."""
+    w_true, w_other = ce_weights(logits.dtype, logits.shape[1], smoothing, eps)
+    return torch.full_like(logits, w_other).scatter_(1, target.long().unsqueeze(1), w_true)
+
+
+def smoothed_cross_entropy(logits, target, smoothing=True, eps=0.2, return_pred=False):
+    """Label-smoothed cross entropy with torch's own kernels (reference
+    loss.py:4-21): soft target times log_softmax, summed over classes, mean
+    over rows; F.cross_entropy without smoothing. (M, C) logits with (M,)
+    labels or (B, C, N) with (B, N)."""
+    if logits.shape[1] < 2:
+        raise ValueError(f"dgx: a cross entropy needs at least 2 classes, got logits {tuple(logits.shape)}")
+    if smoothing:
+        loss = -(ce_target(logits, target, True, eps) * F.log_softmax(logits, dim=1)).sum(dim=1).mean()
+    else:
+        loss = F.cross_entropy(logits, target.long(), reduction="mean")
+    return (loss, logits.detach().max(dim=1)[1]) if return_pred else loss
+
+
 def attention(q, k, v, heads, dropout_p=0.0, scale=None):
     """dropout(softmax(scale q k^T)) v per head on the host (torch's
     scaled_dot_product_attention, the kernel nn.MultiheadAttention uses)."""

@@ -645,6 +645,39 @@ int dgx_adam_step_f32(int n, float* const* params, const float* const* grads, fl
 int dgx_amp_unscale_f32(int n, float* const* grads, const int64_t* numels, const float* inv_scale, float* found_inf,
                         void* stream);
 
+/* ---- loss head: label-smoothed cross entropy (reference loss.py:4-21) of
+ * logits (fp32, fp16 or bf16) against integer labels, mean over the M = B * N
+ * rows. The logits are a (B, C, N) tensor with element strides (sb, sc, sn) in
+ * one of two dense layouts, neither copied: class-contiguous (sc == 1,
+ * sn == C, sb == N * C; an (M, C) matrix is B = 1, N = M) or point-contiguous
+ * (sn == 1, sc == N, sb == C * N). Other strides: DGX_EUNSUPPORTED. C >= 2.
+ * Row i's target puts w_true on class labels[i] and w_other on every other
+ * class (1 and 0: plain cross entropy); the caller passes them as the
+ * reference's target expression rounds them in the logits' dtype. Labels are
+ * int64 (label_is_i64 != 0) or int32 and are only compared with class indices:
+ * a label outside [0, C) makes the loss and that row's gradient NaN.
+ * exp, log and the sums run in fp64 (see csrc/loss.hip); results are rounded
+ * once. */
+#define DGX_CE_F32 0
+#define DGX_CE_F16 1
+#define DGX_CE_BF16 2
+/* Bytes of workspace the forward needs for M rows (per-workgroup partial sums). */
+size_t dgx_smoothed_ce_workspace_bytes(int64_t M);
+/* lse[M] (fp64, kept for the backward), *loss (fp32 mean) and, if pred is not
+ * NULL, pred[M] = each row's arg-max class (smallest index among equal
+ * maxima). Two launches: the row kernel and a one-workgroup sum of its
+ * partials in a fixed order (bitwise reproducible; no atomics, no state that
+ * outlives the call). */
+int dgx_smoothed_ce_fwd(const void* logits, int dtype, int64_t B, int64_t C, int64_t N, int64_t sb, int64_t sc,
+                        int64_t sn, const void* labels, int label_is_i64, float w_true, float w_other, double* lse,
+                        float* loss, int64_t* pred, void* ws, size_t ws_bytes, void* stream);
+/* dlogits = (*g / M) (W softmax(logits) - target), W = w_true + (C - 1) w_other,
+ * in the logits' dtype and layout; g is a device fp32 scalar (the incoming
+ * gradient: a GradScaler's scale), scaled in before the one rounding. One launch. */
+int dgx_smoothed_ce_bwd(const void* logits, int dtype, int64_t B, int64_t C, int64_t N, int64_t sb, int64_t sc,
+                        int64_t sn, const void* labels, int label_is_i64, float w_true, float w_other,
+                        const double* lse, const float* g, void* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
