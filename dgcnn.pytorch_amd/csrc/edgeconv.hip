@@ -299,6 +299,10 @@ __global__ __launch_bounds__(EC_THREADS) void edge_gather_lds_kernel(
                 s[u] *= dir[u];
                 yv[u] = best[u] + q;
                 if (EVAL) {
+                    // the ordered '>' above passes over a NaN neighbour, the reference's
+                    // max (dgcnn.py:86) returns it: the slot sum tells (the training
+                    // form carries it in the BN sums)
+                    yv[u] = (s[u] - s[u] == 0.f) ? yv[u] : NAN;
                     yv[u] = lrelu(fmaf(sgn[u], yv[u], shv[u]), slope);
                 } else if (okc[u]) {
                     acc1[u] += fmaf((float)k, q, s[u]);                      // sum_k y

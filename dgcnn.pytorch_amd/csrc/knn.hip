@@ -25,7 +25,9 @@
 //                     admission bound shared through LDS; 3-channel clouds first
 //                     run a values-only pre-pass that seeds that bound. A (rare)
 //                     row whose list overflowed is recomputed exactly by the
-//                     same block at the end (knn_fix_row).
+//                     same block at the end (knn_fix_row); the rows of a cloud
+//                     with a NaN / inf coordinate in torch.topk's total order
+//                     (knn_total_row), so every id written is in [0, N).
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -428,6 +430,83 @@ __device__ void knn_fix_row(float* fixa, const float* __restrict__ ib, const flo
     __syncthreads();  // the fix-up area is free for the next row
 }
 
+// ------------------------------------------------- non-finite rows ----
+// torch.topk's order (the reference, dgcnn.py:11): NaN ranks above every
+// number, then value descending; equal values and NaNs by index ascending. On
+// finite values this is canon_better.
+__device__ __forceinline__ bool total_better(float av, int aj, float bv, int bj) {
+    const bool an = av != av, bn = bv != bv;
+    if (an || bn) return an && (!bn || aj < bj);
+    return canon_better(av, aj, bv, bj);
+}
+
+// One query row qf by k rounds of a total-order arg-max over re-streamed values
+// (knn_fix_row's slow path with total_better): every rank is written and every
+// id is a candidate's, whatever the values are. Called block-uniformly for the
+// rows the selection cannot serve: its ordered compares never admit a NaN
+// score and a -inf one never displaces the lists' (-inf, 0x7fffffff) pads, so a
+// row with fewer than k scores above -inf would write pads as ids. The same
+// MFMA chain on the same operands: on finite values the selection's result.
+template <int NSTEP>
+__device__ __attribute__((noinline)) void knn_total_row(float* area, const float* __restrict__ ib,
+                                                        const float* __restrict__ xib,
+                                                        const float* __restrict__ xxb, int N, int k, int qf,
+                                                        int64_t row, int64_t* __restrict__ idx64,
+                                                        int32_t* __restrict__ idx32, float* __restrict__ vals) {
+#pragma clang fp contract(off)
+    float* bestv = area;                                   // [KQ_WAVES]
+    int* bestj = reinterpret_cast<int*>(area + KQ_WAVES);  // [KQ_WAVES]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, ql = lane & 15;
+    const int ntile = (N + 15) >> 4;
+    float bq[NSTEP];
+    ld_lane<NSTEP, NSTEP>(ib + (int64_t)(qf >> 4) * 64 * NSTEP, g * 16 + knn_row(qf & 15), 0, bq);
+#pragma unroll
+    for (int t = 0; t < NSTEP; ++t) bq[t] *= 2.0f;
+    const float xxq = xxb[qf];
+    float pv = __builtin_nanf("");   // (NaN, -1): above every candidate
+    int pj = -1;
+    for (int r = 0; r < k; ++r) {
+        float bv = -INFINITY;        // (-inf, 0x7fffffff): below every candidate
+        int bj = 0x7fffffff;
+        for (int s = wave; s < ntile; s += KQ_WAVES) {
+            float a[NSTEP];
+            ld_lane<NSTEP, NSTEP>(ib + (int64_t)s * 64 * NSTEP, lane, 0, a);
+            const float4 xc = *reinterpret_cast<const float4*>(xib + s * 16 + 4 * g);
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < NSTEP; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], bq[t], acc, 0, 0, 0);
+            const float xcv[4] = {xc.x, xc.y, xc.z, xc.w};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {   // all 16 columns are the same query: column 0 speaks
+                const int j = s * 16 + g + 4 * u;
+                const float v = (acc[u] - xcv[u]) - xxq;
+                if (ql == 0 && j < N && total_better(pv, pj, v, j) && total_better(v, j, bv, bj)) { bv = v; bj = j; }
+            }
+        }
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oj = __shfl_xor(bj, o);
+            if (total_better(ov, oj, bv, bj)) { bv = ov; bj = oj; }
+        }
+        __syncthreads();  // the previous round's picks are read
+        if (lane == 0) { bestv[wave] = bv; bestj[wave] = bj; }
+        __syncthreads();
+        pv = bestv[0];
+        pj = bestj[0];
+#pragma unroll
+        for (int w = 1; w < KQ_WAVES; ++w)
+            if (total_better(bestv[w], bestj[w], pv, pj)) { pv = bestv[w]; pj = bestj[w]; }
+        // k <= N: a candidate below the previous pick always exists, so pj < N
+        if (tid == 0) {
+            if (idx64) idx64[row * k + r] = pj;
+            if (idx32) idx32[row * k + r] = pj;
+            if (vals) vals[row * k + r] = pv;
+        }
+    }
+    __syncthreads();  // the area is free for the next row
+}
+
 // ------------------------------------------------------------ knn kernel ----
 // Block = KQ_GROUPS wave groups x 2 candidate halves, one wave each; a wave
 // serves QG groups of 16 queries (QG = 2: 32 queries per wave, 64 per block).
@@ -812,6 +891,15 @@ void knn_kernel(const float* __restrict__ img, const float* __restrict__ xximg, 
 #endif
     flush();
 
+    // A point with a non-finite |x|^2 (a NaN or inf coordinate) gives every row
+    // of its cloud a NaN or -inf score, which the ordered compares above never
+    // admitted: such a cloud's rows are all redone in torch.topk's total order
+    // (knn_total_row). One pass over the cloud's |x|^2 image (values >= 0, NaN
+    // or inf, so the sum tells; one that overflows only sends a finite cloud
+    // down the exact slow path), loaded here and read after the merge.
+    // (the first chunk is in flight during the merge; N > 1024 has more)
+    const float4 xx0 = *reinterpret_cast<const float4*>(xib + min(4 * tid, 16 * ntile - 4));
+
     // Merge the wave's 4 lists of each query (lanes ql, ql+16, ql+32, ql+48)
     // by k rounds of a canonical arg-max over the 4 list heads; the winning
     // lane pops its head. Rank r ends up in lane r % 4. The groups' merges are
@@ -857,11 +945,19 @@ void knn_kernel(const float* __restrict__ img, const float* __restrict__ xximg, 
             if (r < k) lists[(h * QPB + S.qq) * KB + r] = make_float2(S.ov[t], __int_as_float(S.oj[t]));
         }
     });
+    __shared__ int cloud_bad;
     if (tid < QPB) {
         kth[tid] = -INFINITY;
         flg[tid] = 0;
     }
+    if (tid == 0) cloud_bad = 0;
+    float xxsum = (xx0.x + xx0.y) + (xx0.z + xx0.w);
+    for (int e = 4 * (tid + KQ_THREADS); e < 16 * ntile; e += 4 * KQ_THREADS) {
+        const float4 q = *reinterpret_cast<const float4*>(xib + e);
+        xxsum += (q.x + q.y) + (q.z + q.w);
+    }
     __syncthreads();
+    if (!(xxsum < INFINITY)) cloud_bad = 1;
     each([&](Grp& S, int) {
         const float2* other = lists + ((1 - h) * QPB + S.qq) * KB;
 #pragma unroll
@@ -883,15 +979,17 @@ void knn_kernel(const float* __restrict__ img, const float* __restrict__ xximg, 
     });
     __syncthreads();
     each([&](Grp& S, int) {
-        // A lane whose list was full and whose last kept value reaches the merged
-        // k-th may have dropped a member of the true top-k: mark the row for the
-        // exact fix-up pass.
         const float kv = kth[S.qq];
-        if (S.last != -INFINITY && S.last >= kv) flg[S.qq] = 1;
-        // fewer than k candidates reached the seed (the merged k-th is then a -inf
-        // pad): only a seed that is not a value of this kernel's arithmetic does
-        // that; the exact fix-up from T0 = -inf repairs the row
-        if (!(kv >= S.tseed)) flg[S.qq] = 1;
+        // A cloud with a non-finite point, or fewer than k scores above -inf
+        // (products that overflow although every |x|^2 is finite: the merged k-th
+        // is a pad or was never set): the total-order pass writes the row (every
+        // lane of the row agrees, so 1 and 2 never race).
+        if (cloud_bad != 0 || !(kv > -INFINITY)) flg[S.qq] = 2;
+        // A lane whose list was full and whose last kept value reaches the merged
+        // k-th may have dropped a member of the true top-k; fewer than k candidates
+        // reached the seed (only a seed that is not a value of this kernel's
+        // arithmetic does that): the exact fix-up pass repairs the row.
+        else if ((S.last != -INFINITY && S.last >= kv) || !(kv >= S.tseed)) flg[S.qq] = 1;
     });
     __syncthreads();
     each([&](Grp& S, int) {
@@ -920,9 +1018,17 @@ void knn_kernel(const float* __restrict__ img, const float* __restrict__ xximg, 
 #endif
     // the block's flagged rows (rare), one at a time; flg / kth are block-uniform LDS reads
     float* fixa = smem + KQ_HALVES * QPB * KB * 2 + 2 * QPB;
-    for (int f = 0; f < QPB; ++f) {
+    static_assert(QPB <= 64, "one flag per lane");
+    const int fl = (lane < QPB && qb * QPB + lane < N) ? flg[lane] : 0;
+    uint64_t todo = __ballot(fl != 0);        // the same LDS words in every wave: block-uniform
+    const uint64_t total = __ballot(fl == 2);
+    while (todo != 0) {
+        const int f = __builtin_ctzll(todo);
+        todo &= todo - 1;
         const int qf = qb * QPB + f;
-        if (flg[f] != 0 && qf < N)
+        if ((total >> f) & 1)
+            knn_total_row<NSTEP>(fixa, ib, xib, xx + (int64_t)b * N, N, k, qf, (int64_t)b * N + qf, idx64, idx32, vals);
+        else
             knn_fix_row<NSTEP>(fixa, ib, xib, xx + (int64_t)b * N, N, k, qf, kth[f], (int64_t)b * N + qf, idx64,
                                idx32, vals);
     }

@@ -104,8 +104,15 @@ __device__ __forceinline__ uint32_t fkey(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// torch.topk's order (the reference, dgcnn.py:11) as a key: a NaN of either
+// sign ranks above every number. The select and the sort both rank by this
+// key, a total order, so a NaN score cannot leave a rank to a pad
+__device__ __forceinline__ uint32_t tkey(float f) { return f != f ? 0xffffffffu : fkey(f); }
+
+// (key desc, index asc): on numbers (value desc, index asc), -0 folded into +0 by pdv
 __device__ __forceinline__ bool canon_better_g(float va, int ia, float vb, int ib) {
-    return va > vb || (va == vb && ia < ib);
+    const uint32_t ka = tkey(va), kb = tkey(vb);
+    return ka > kb || (ka == kb && ia < ib);
 }
 
 // block-wide exclusive prefix of one flag per thread (returns the thread's offset; *total = block sum)
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_select_generic_kernel(const fl
         hist[t] = 0;   // KG_THREADS == 256 bins
         __syncthreads();
         for (int j = t; j < N; j += KG_THREADS) {
-            const uint32_t key = fkey(pdv(j));
+            const uint32_t key = tkey(pdv(j));
             if ((key & hmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -177,7 +184,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_select_generic_kernel(const fl
     __syncthreads();
     for (int j = t; j < N; j += KG_THREADS) {
         const float v = pdv(j);
-        if (fkey(v) > T) pairs[atomicAdd(&cnt_gt, 1)] = make_float2(v, __int_as_float(j));
+        if (tkey(v) > T) pairs[atomicAdd(&cnt_gt, 1)] = make_float2(v, __int_as_float(j));
     }
     // ties at the k-th value in index order
     int taken = 0;
@@ -187,7 +194,7 @@ __global__ __launch_bounds__(KG_THREADS) void knn_select_generic_kernel(const fl
         int flag = 0;
         if (j < N) {
             v = pdv(j);
-            flag = fkey(v) == T;
+            flag = tkey(v) == T;
         }
         int tot;
         const int pos = taken + block_prefix(flag, wsum, &tot);

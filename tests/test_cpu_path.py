@@ -175,3 +175,52 @@ def test_cpu_net_golden(monkeypatch):
     y = net(torch.from_numpy(g["x"]), torch.from_numpy(g["lbl"]))
     assert y.device.type == "cpu" and tuple(y.shape) == g["out"].shape
     assert rel_err(y.detach(), g["out"]) < 1e-3
+
+
+# ---- non-finite values on the host path (DESIGN "Non-finite values") ----------------------------------------------
+@pytest.mark.parametrize("pattern", ["nan_point", "nan_coordinate", "inf_minus_inf", "every_point"])
+@pytest.mark.parametrize("layout", ["bcn", "perm"])
+def test_cpu_knn_ids_valid_for_nonfinite_input(layout, pattern):
+    """Host kNN on a cloud with NaN / inf coordinates: ids in [0, N), the clean
+    cloud's ids unchanged, and (torch's NaN-first order) a point whose score is
+    NaN is a neighbour of every finite row."""
+    from dgx import synth
+    from models.dgcnn import knn
+    N, k = 77, 12
+    clean = synth.cube_clouds(2, N, 5)
+    pts = clean.copy()
+    if pattern == "nan_point":
+        pts[0, 40, :] = np.nan
+    elif pattern == "nan_coordinate":
+        pts[0, N - 1, 1] = np.nan
+    elif pattern == "inf_minus_inf":
+        pts[0, 0, 0], pts[0, 0, 1] = np.inf, -np.inf
+    else:
+        pts[0, :, 2] = np.nan
+    idx = knn(_cpu_view(pts, layout), k)
+    assert int(idx.min()) >= 0 and int(idx.max()) < N
+    assert torch.equal(idx[1], knn(_cpu_view(clean, layout), k)[1])
+    x = torch.from_numpy(pts[0]).t().unsqueeze(0)
+    pd = -torch.sum(x ** 2, dim=1, keepdim=True) + 2 * torch.matmul(x.transpose(2, 1), x) \
+        - torch.sum(x ** 2, dim=1, keepdim=True).transpose(2, 1)
+    nan_score = torch.isnan(pd[0])
+    member = torch.zeros(N, N, dtype=torch.bool).scatter_(1, idx[0], True)
+    rows = torch.from_numpy(np.isfinite(pts[0]).all(1)) & (nan_score.sum(1) <= k)
+    assert not bool((nan_score & ~member)[rows].any())
+
+
+@pytest.mark.parametrize("train", [True, False])
+def test_cpu_dgcnn_keeps_nan_point(train):
+    """DGCNN on host tensors with one NaN point in cloud 0: the output of that
+    cloud is non-finite, as the reference's is (eval: the clean cloud stays finite)."""
+    from dgx import synth
+    from models.dgcnn import DGCNN
+    torch.manual_seed(0)
+    m = DGCNN(types.SimpleNamespace(emb_dim=64, k=10)).train(train)
+    x = torch.from_numpy(synth.cube_clouds(2, 64, 3)).permute(0, 2, 1).contiguous()
+    x[0, :, 9] = float("nan")
+    with torch.no_grad():
+        y = m(x)
+    assert not bool(torch.isfinite(y[0]).all())
+    if not train:
+        assert bool(torch.isfinite(y[1]).all())
