@@ -1,10 +1,10 @@
 // libdgx_torch.so — the PyTorch-ROCm C++ layer of the engine and the ONE place
-// the EdgeConv / conv5 launch schedule lives.
+// the launch schedule and its BatchNorm bookkeeping live.
 //
 // Every launch goes to libdgx.so's C ABI (include/dgx.h) straight from C++.
-// The schedule of DGCNN's EdgeConv chain (reference models/dgcnn.py:84-100)
-// and of its conv5 (dgcnn.py:74-78, 100-102), forward and backward, in every
-// configuration the reference's scripts run it in:
+// The schedule of DGCNN's EdgeConv chain (reference models/dgcnn.py:84-100),
+// of its conv5 (dgcnn.py:74-78, 100-102) and of PositionEmbedding's per-edge
+// MLP (models/layers.py:45-52), forward and backward, in every configuration the reference's scripts run it in:
 //   precision   bf16 GEMM operands (BASELINE cfg2; what torch.autocast asks for,
 //               main_partseg_dist.py:253) or the fp32 parity mode;
 //   BatchNorm   training (batch statistics, running-stat update with a momentum
@@ -18,6 +18,9 @@
 //   chain_forward / chain_backward        the block chain (dgx.edgeconv's
 //                                         autograd Function and dgx::edgeconv_chain call these)
 //   pointconv_forward / pointconv_backward conv5 + BN + LeakyReLU (dgx.pointconv, dgx::pointconv)
+//   edge_mlp2_forward / edge_mlp2_backward PositionEmbedding's edge MLP (dgx.edgemlp, dgx::edge_mlp2);
+//                                         its kNN graph comes in from the caller
+//   bn_batch_stats / bn_backward_consts   one layer's BatchNorm finalize, forward / backward (dgx.bn)
 //   dgcnn                                 DGCNN.forward as one op with a C++ autograd node
 //                                         (eager training: ~60 launches without a Python frame)
 //   knn_timing                            per-thread HIP-event timing of the kNN selection launches
@@ -35,6 +38,7 @@
 #include <cstdint>
 #include <optional>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -117,7 +121,7 @@ thread_local bool t_knn_timing = false;
 thread_local std::vector<KnnRec> t_knn_recs;
 
 // ------------------------------------------------------------ BatchNorm ----
-// The nn.BatchNorm fields the schedule reads (dgx.bn), per layer.
+// The nn.BatchNorm fields the schedule reads (dgx.bn.op_args), per layer.
 struct BnSpec {
   bool training = true, track = true;
   Tensor rm, rv, nbt;              // module buffers, read (undefined when absent)
@@ -129,7 +133,7 @@ struct BnSpec {
   bool update() const { return training && track && rm.defined(); }
 };
 
-// per-channel state of one BN layer (dgx.bn.Stats)
+// per-channel state of one BN layer (dgx.bn.Stats names the same fields)
 struct Stats {
   Tensor scale, shift, mean, invstd;
   std::string group;
@@ -168,7 +172,7 @@ std::vector<BnSpec> parse_bn(const std::vector<std::optional<Tensor>>& bn_t, con
   return out;
 }
 
-// dgx.bn._compact: a tall (rows, 2, co) partial array pre-reduced to ~128 rows
+// a tall (rows, 2, co) partial array pre-reduced to ~128 rows
 std::pair<Tensor, int> compact(const Dev& d, const Tensor& partials, int rows, int co) {
   if (rows <= 1024) return {partials, rows};
   const int R = 128, S = rows / R, left = rows - S * R;
@@ -179,7 +183,7 @@ std::pair<Tensor, int> compact(const Dev& d, const Tensor& partials, int rows, i
 }
 
 // SyncBatchNorm: [global sums (2, C) | global count] in fp64 after ONE all-reduce
-// over the module's process group (dgx.dist.allreduce_sums); the count stays on
+// over the module's process group; the count stays on
 // the device for the fp64 finalize kernels (no host synchronisation)
 Tensor allreduce_sums(const Dev& d, const Tensor& partials, int rows, int co, double count, const std::string& group) {
   Tensor buf = at::empty({2 * co + 1}, d.f64);
@@ -197,7 +201,7 @@ Tensor allreduce_sums(const Dev& d, const Tensor& partials, int rows, int co, do
   return buf;
 }
 
-// dgx.bn.batch_stats: batch mean / var from per-block (sum y, sum y^2) partials
+// batch mean / var from per-block (sum y, sum y^2) partials
 // over `count` elements; running statistics updated as nn.BatchNorm would
 Stats batch_stats(const Dev& d, const Tensor& partials, int rows, double count, const Tensor& gamma,
                   const Tensor& beta, const BnSpec& bn) {
@@ -242,7 +246,7 @@ Stats batch_stats(const Dev& d, const Tensor& partials, int rows, double count, 
   return st;
 }
 
-// dgx.bn.running_stats: eval-mode affine from the running statistics
+// eval-mode affine from the running statistics
 Stats running_stats(const Dev& d, const Tensor& gamma, const Tensor& beta, const BnSpec& bn) {
   const int co = (int)gamma.size(0);
   TORCH_CHECK(bn.rm.defined() && bn.rv.defined(), "dgx: running statistics missing for an eval-mode BatchNorm");
@@ -257,7 +261,7 @@ Stats running_stats(const Dev& d, const Tensor& gamma, const Tensor& beta, const
   return st;
 }
 
-// dgx.bn.backward_consts: (dgamma, dbeta, c0, c1) from (sum g, sum g*yhat) partials
+// (dgamma, dbeta, c0, c1) from (sum g, sum g*yhat) partials
 std::array<Tensor, 4> backward_consts(const Dev& d, const Tensor& partials, int rows, double count, const Stats& st) {
   const int co = (int)st.scale.size(0);
   std::array<Tensor, 4> r{at::empty({co}, d.f32), at::empty({co}, d.f32), at::empty({co}, d.f32),
@@ -384,7 +388,23 @@ void mm_atb(const Dev& d, const Tensor& a, const Tensor& b, Tensor& out, int spl
   reduce_slab(d, slab, used, M, N, split_rows > 0 ? split_rows : M, out, defer);
 }
 
-// dgx.gemm.lds_ok_nt: whether the LDS-DMA path takes this k-contiguous bf16 operand
+// out (M,N) = a (M,K) b (K,N), fp32 or bf16 operands rounded to bf16 while staged; transposed
+// views are read in place, the weight-gradient form (a long reduction over rows) is split-K
+Tensor mm16(const Dev& d, Tensor a, Tensor b) {
+  const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(1);
+  if (a.stride(1) != 1 && a.stride(0) != 1) a = a.contiguous();
+  if (b.stride(1) != 1 && b.stride(0) != 1) b = b.contiguous();
+  const bool a_ic = a.stride(1) != 1, b_ic = b.stride(1) == 1;
+  Tensor A = a_ic ? a.t() : a, Bv = b_ic ? b : b.t();
+  Tensor out = at::empty({M, N}, d.f32);
+  if (K >= 2048 && a_ic && b_ic)
+    mm_atb(d, A, Bv, out, 0, nullptr);
+  else
+    gemm16(d, A, a_ic, Bv, b_ic, M, N, K, kEpiStore, P(out), out.stride(0), nullptr, 1);
+  return out;
+}
+
+// whether the LDS-DMA path takes this k-contiguous bf16 operand
 bool lds_ok(const Tensor& x16, int64_t K) {
   return x16.defined() && x16.numel() && is16(x16) && K % 64 == 0 && x16.stride(0) % 8 == 0 &&
          reinterpret_cast<uintptr_t>(x16.data_ptr()) % 16 == 0;
@@ -553,7 +573,15 @@ std::vector<std::pair<Tensor, Tensor>> prep_views(const Tensor& buf, const std::
   return v;
 }
 
-// dgx.gemm.prep_weights: every job's bf16 copies in one launch
+// one plain weight's bf16 copies: (nt (rows, cols), tn (cols, rows))
+std::pair<Tensor, Tensor> prep_weight(const Dev& d, const Tensor& w, int rows, int cols) {
+  Tensor nt = at::empty({rows, cols}, d.bf16), tn = at::empty({cols, rows}, d.bf16);
+  Tensor wc = w.contiguous();
+  check(dgx_weight_prep_bf16(P(wc), rows, cols, 0, nt.data_ptr(), tn.data_ptr(), d.stream), "weight prep");
+  return {nt, tn};
+}
+
+// every job's bf16 copies in one launch
 std::pair<Tensor, std::vector<std::pair<Tensor, Tensor>>> prep_weights(const Dev& d, const std::vector<PrepJob>& jobs) {
   TORCH_CHECK(jobs.size() <= 8, "dgx weight prep: at most 8 weights per launch");
   int64_t total = 0;
@@ -1139,10 +1167,7 @@ Tensor pointconv_forward_impl(const Dev& d, const Tensor& X_in, const Tensor& X1
     if (X16.defined() && X16.numel() && lds_ok(X16, K)) {
       Xop = X16;
       if (!nt.defined() || !nt.numel()) {
-        nt = at::empty({Co, K}, d.bf16);
-        tn = at::empty({K, Co}, d.bf16);
-        Tensor wc = W.contiguous();
-        check(dgx_weight_prep_bf16(P(wc), Co, (int)K, 0, nt.data_ptr(), tn.data_ptr(), d.stream), "weight prep");
+        std::tie(nt, tn) = prep_weight(d, W, Co, (int)K);
       }
       Z = use_batch ? lds_xwt(d, X16, nt, &gemm_part, true) : lds_xwt(d, X16, nt, nullptr, false);
     } else {
@@ -1399,6 +1424,298 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pointconv_backward(const Tensor& dout
   return {r[0], r[1].view(weight.sizes()), r[2], r[3]};
 }
 
+// ------------------------------------------ PositionEmbedding's edge MLP ----
+// max_k conv2(conv1(get_graph_feature(x, k))) of reference models/layers.py:45-52 (dgx.edgemlp)
+// as one stage. The edge tensor is never built: conv1 is PQ = X [W1; W2]^T (y_e = P_j + Q_i, as
+// in the chain) with its BN statistics from the EdgeConv gather kernel.
+//   bf16, C1 = 64, C2 in {64, 128}, k <= 64: ONE forward kernel builds each 16-edge h1 tile,
+//   runs conv2 on the MFMA and keeps the max over k and the BN2 statistics (h1, z2 never reach
+//   HBM); with C2 = 128 ONE backward kernel recomputes them and forms gE, the BN1 partials
+//   and dW2; otherwise h1 is kept for the dZ2 / dH1 GEMMs;
+//   every other shape and the fp32 mode: h1 per edge row, conv2 as one GEMM over the E = B*N*k
+//   rows, max over k, dense dZ2, the two conv2 GEMMs, LReLU/BN1 backward in place.
+// Then the gather over the kNN graph and its reverse forms dP / dQ. The fp32 mode is exact
+// fp32 here whatever the opts word says of split GEMMs.
+// the saved list (dgx.schedule.EMLP_FIELDS): absent tensors travel as empty ones
+enum EmlpField { kEX, kEIdx, kEPQ, kESumP, kEH1, kEZ2, kEYsel, kEArg, kEScale1, kEShift1, kEMean1, kEInvstd1,
+                 kEScale2, kEShift2, kEMean2, kEInvstd2, kENt, kETn, kNumEmlpFields };
+const char* const kEmlpNames[kNumEmlpFields] = {"X",      "idx",    "PQ",      "sumP",   "H1",     "Z2",
+                                                "ysel",   "arg",    "scale1",  "shift1", "mean1",  "invstd1",
+                                                "scale2", "shift2", "mean2",   "invstd2", "nt",    "tn"};
+
+bool emlp_fused_bwd_ok(bool fused_bwd, bool bf16, int C1, int C2, int k) {
+  return fused_bwd && bf16 && C1 == 64 && C2 == 128 && k <= 64;
+}
+
+// dgx_host::edge_mlp2_forward -> (out (B, C2, N), saved). idx: the kNN graph (int32 (B, N, k)) the
+// caller found on x or on its knn_src; bn lists: the two layers'; fused_bwd: dgx.edgemlp.FUSED_BWD
+std::tuple<Tensor, std::vector<Tensor>> edge_mlp2_forward(
+    const Tensor& x_in, const Tensor& idx, int64_t k64, const Tensor& w1, const Tensor& g1, const Tensor& b1,
+    const Tensor& w2, const Tensor& g2, const Tensor& b2, const c10::List<std::optional<Tensor>>& bn_t_l,
+    std::vector<double> bn_f, std::vector<int64_t> bn_i, std::vector<std::string> groups, bool bf16, bool need_grad,
+    bool fused_bwd) {
+  TORCH_CHECK(x_in.is_cuda() && x_in.dim() == 3, "dgx edge MLP: (B, C, N) device input expected");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x_in.device());
+  Dev d(x_in);
+  Tensor x = x_in.to(at::kFloat);
+  const int B = (int)x.size(0), C = (int)x.size(1), N = (int)x.size(2), k = (int)k64;
+  const int64_t M = (int64_t)B * N, E = M * k;
+  const int C1 = (int)w1.size(0), C2 = (int)w2.size(0);
+  TORCH_CHECK(w1.numel() == (int64_t)C1 * 2 * C && w2.numel() == (int64_t)C2 * C1 && g1.numel() == C1 &&
+                  b1.numel() == C1 && g2.numel() == C2 && b2.numel() == C2,
+              "dgx edge MLP: conv / BatchNorm parameter shapes do not match the input");
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.is_contiguous() && idx.dim() == 3 && idx.size(0) == B &&
+                  idx.size(1) == N && idx.size(2) == k,
+              "dgx edge MLP: idx must be contiguous int32 (B, N, k)");
+  auto bns = parse_bn(to_vec(bn_t_l), bn_f, bn_i, groups, 2, 6);
+  const float slope1 = (float)bn_f[2], slope2 = (float)bn_f[5];
+  const bool use1 = bns[0].use_batch(), use2 = bns[1].use_batch();
+  Tensor X = x.permute({0, 2, 1}).reshape({M, C}).contiguous();   // B = 1 reshapes to a column-major view
+  Tensor w1s = split_weight(w1, C, C1), PQ;
+  if (C <= kSmallKMax) {   // raw coordinates (K = 3): exact fp32 in every mode
+    PQ = at::empty({M, 2 * C1}, d.f32);
+    check(dgx_gemm_smallk_f32(P(X), M > 1 ? X.stride(0) : C, P(w1s), (int)M, 2 * C1, C, P(PQ), 2 * C1, d.stream),
+          "gemm small-k");
+  } else {
+    PQ = bf16 ? mm_xwt(d, X, w1s, nullptr) : mm32(d, X, w1s.t(), nullptr, false);
+  }
+  Tensor W2 = w2.reshape({C2, C1});
+  // ---- conv1: BN1 statistics over all E edges
+  Stats st1, st2;
+  Tensor sumP1;
+  if (use1) {
+    Tensor ysel1 = at::empty({M, C1}, d.f32), arg1 = at::empty({M, C1}, d.u8);
+    sumP1 = at::empty({M, C1}, d.f32);
+    const int prow = dgx_edge_partials_rows(B, N, C1);
+    Tensor part1 = at::empty({prow, 2, C1}, d.f32);
+    check(dgx_edge_fwd_gather_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(idx), B, N, k, C1, P(g1), P(ysel1),
+                                  P<uint8_t>(arg1), P(sumP1), P(part1), prow, d.stream),
+          "edge gather");
+    st1 = batch_stats(d, part1, prow, (double)E, g1, b1, bns[0]);
+  } else {
+    st1 = running_stats(d, g1, b1, bns[0]);
+    // sum_k P_j only enters the train-mode BN1 backward (c1 = 0 here)
+    if (need_grad) sumP1 = at::zeros({M, C1}, d.f32);
+  }
+  Tensor H1, Z2, nt, tn;
+  Tensor ysel = at::empty({M, C2}, d.f32), arg = at::empty({M, C2}, d.u8);
+  if (bf16 && C1 == 64 && (C2 == 64 || C2 == 128) && k <= 64) {
+    // h1 -> conv2 (MFMA) -> max over k + BN2 statistics in one kernel: z2 never reaches HBM;
+    // h1 (bf16) is written only for the unfused backward's GEMMs (the fused backward rebuilds it)
+    std::tie(nt, tn) = prep_weight(d, W2, C2, C1);
+    Tensor dir2 = at::where(g2 < 0, -1.0, 1.0).to(at::kFloat).contiguous();
+    Tensor W2d = (W2 * dir2.view({C2, 1})).to(at::kBFloat16).contiguous();
+    if (need_grad && !emlp_fused_bwd_ok(fused_bwd, bf16, C1, C2, k)) H1 = at::empty({E, C1}, d.bf16);
+    const int rows2 = dgx_edge_mlp_fused_rows(B, N);
+    Tensor part2 = at::empty({rows2, 2, C2}, d.f32);
+    check(dgx_edge_mlp_fused_fwd_bf16(P(PQ), 2 * C1, P<int32_t>(idx), B, N, k, C1, C2, P(st1.scale), P(st1.shift),
+                                      slope1, W2d.data_ptr(), P(dir2), P(ysel), P<uint8_t>(arg), P(part2), rows2,
+                                      H1.defined() ? H1.data_ptr() : nullptr, d.stream),
+          "edge mlp fused forward");
+    st2 = use2 ? batch_stats(d, part2, rows2, (double)E, g2, b2, bns[1]) : running_stats(d, g2, b2, bns[1]);
+  } else {
+    const bool h16 = bf16 && C1 % 64 == 0;
+    H1 = at::empty({E, C1}, h16 ? d.bf16 : d.f32);
+    check(dgx_edge_mlp_h1_f32(P(PQ), 2 * C1, P<int32_t>(idx), B, N, k, C1, P(st1.scale), P(st1.shift), slope1,
+                              H1.data_ptr(), (int)h16, d.stream),
+          "edge h1");
+    // ---- conv2: one GEMM over the edge rows (+ BN2 column statistics)
+    Tensor part2;
+    if (h16) {
+      std::tie(nt, tn) = prep_weight(d, W2, C2, C1);
+      Z2 = use2 ? lds_xwt(d, H1, nt, &part2, true) : lds_xwt(d, H1, nt, nullptr, false);
+    } else if (bf16) {
+      Z2 = mm_xwt(d, H1, W2, use2 ? &part2 : nullptr);
+    } else {
+      Z2 = mm32(d, H1, W2.t(), nullptr, false);
+      if (use2) {
+        const int rows = dgx_colstats_rows(E);
+        part2 = at::empty({rows, 2, C2}, d.f32);
+        check(dgx_colstats_f32(P(Z2), C2, E, C2, P(part2), rows, d.stream), "colstats");
+      }
+    }
+    st2 = use2 ? batch_stats(d, part2, (int)part2.size(0), (double)E, g2, b2, bns[1])
+               : running_stats(d, g2, b2, bns[1]);
+    // ---- max over k (layers.py:52) of LReLU(BN2(z2)): select, then apply
+    check(dgx_edge_mlp_max_f32(Z2.data_ptr(), (int)is16(Z2), B, N, k, C2, P(st2.scale), P(ysel), P<uint8_t>(arg),
+                               d.stream),
+          "edge max");
+  }
+  // LReLU(BN2) of the selected values, written (B, C2, N) contiguous as the reference's max
+  // over k returns it (LDS-transposed apply)
+  Tensor out = at::empty({B, C2, N}, d.f32);
+  check(dgx_pointconv_apply_f32(P(ysel), C2, B, N, C2, P(st2.scale), P(st2.shift), slope2, P(out), d.stream),
+        "bn apply");
+  auto e = [&](const Tensor& t) { return t.defined() ? t : at::empty({0}, d.f32); };
+  return {out, {X, idx, PQ, e(sumP1), e(H1), e(Z2), ysel, arg, st1.scale, st1.shift, st1.mean, st1.invstd, st2.scale,
+                st2.shift, st2.mean, st2.invstd, e(nt), e(tn)}};   // EmlpField order
+}
+
+// dgx_host::edge_mlp2_backward -> (dx or empty, dW1, dgamma1, dbeta1, dW2, dgamma2, dbeta2)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> edge_mlp2_backward(
+    const Tensor& dout_in, std::vector<Tensor> S, const Tensor& w1, const Tensor& w2, std::vector<int64_t> shape,
+    int64_t k64, std::vector<int64_t> eval, std::vector<std::string> groups, std::vector<double> slopes, bool bf16,
+    bool x_needs_grad, int64_t opts) {
+  TORCH_CHECK(S.size() == kNumEmlpFields && shape.size() == 3 && eval.size() == 2 && groups.size() == 2 &&
+                  slopes.size() == 2,
+              "dgx edge MLP backward: saved state does not match the stage");
+  const Tensor &X = S[kEX], &idx = S[kEIdx], &PQ = S[kEPQ], &sumP1 = S[kESumP], &H1 = S[kEH1], &Z2 = S[kEZ2];
+  const Tensor &ysel = S[kEYsel], &arg = S[kEArg], &nt = S[kENt], &tn = S[kETn];
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  Dev d(X);
+  const Stats st1{S[kEScale1], S[kEShift1], S[kEMean1], S[kEInvstd1], groups[0], eval[0] != 0};
+  const Stats st2{S[kEScale2], S[kEShift2], S[kEMean2], S[kEInvstd2], groups[1], eval[1] != 0};
+  const int B = (int)shape[0], C = (int)shape[1], N = (int)shape[2], k = (int)k64;
+  const int64_t M = (int64_t)B * N, E = M * k;
+  const int C1 = (int)w1.size(0), C2 = (int)w2.size(0);
+  TORCH_CHECK(X.size(0) == M && X.size(1) == C && idx.numel() == E && PQ.size(0) == M && PQ.size(1) == 2 * C1 &&
+                  sumP1.numel() == M * C1 && ysel.numel() == M * C2 && arg.numel() == M * C2 &&
+                  dout_in.numel() == M * C2 && dout_in.dim() == 3 && dout_in.size(1) == C2,
+              "dgx edge MLP backward: saved state does not match the shapes");
+  const float slope1 = (float)slopes[0], slope2 = (float)slopes[1];
+  const bool fused = Z2.numel() == 0;                // fused forward: z2 was never stored
+  const bool fused_bwd = fused && H1.numel() == 0;   // ... and h1 neither: the fused backward kernel
+  const bool z16 = fused || is16(Z2);
+  const bool have_prep = nt.numel() > 0;
+  TORCH_CHECK(fused_bwd || (H1.size(0) == E && H1.size(1) == C1), "dgx edge MLP backward: h1 does not match");
+  TORCH_CHECK(fused || (Z2.size(0) == E && Z2.size(1) == C2), "dgx edge MLP backward: z2 does not match");
+  TORCH_CHECK(!fused || (have_prep && C1 == 64 && (!fused_bwd || C2 == 128)),
+              "dgx edge MLP backward: the fused kernels' state expected");
+  Tensor dout = dout_in.to(at::kFloat);
+  Tensor dY_pm = dout.permute({0, 2, 1});   // (B, N, C2): point-major if the gradient came that way
+  // ---- BN2 + LReLU backward at the selected edges, then dense over all edges
+  Tensor dz = at::empty({M, C2}, d.f32), part;
+  int nblk;
+  if (dY_pm.is_contiguous()) {
+    nblk = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (M + 63) / 64));
+    part = at::empty({nblk, 2, C2}, d.f32);
+    check(dgx_edge_bwd_dz_f32(P(dY_pm), C2, P(ysel), (int)M, C2, P(st2.scale), P(st2.shift), P(st2.mean),
+                              P(st2.invstd), slope2, P(dz), P(part), nblk, d.stream),
+          "edge bwd dz");
+  } else {   // (B, C2, N) gradient (a contiguous downstream): read channel-major, no transpose copy
+    Tensor dcm = dout.contiguous();
+    nblk = dgx_edge_bwd_dz_cm_rows(B, N);
+    part = at::empty({nblk, 2, C2}, d.f32);
+    check(dgx_edge_bwd_dz_cm_f32(P(dcm), P(ysel), B, N, C2, P(st2.scale), P(st2.shift), P(st2.mean), P(st2.invstd),
+                                 slope2, P(dz), P(part), nblk, d.stream),
+          "edge bwd dz");
+  }
+  auto c2 = backward_consts(d, part, nblk, (double)E, st2);   // dgamma2, dbeta2, c0, c1
+  Tensor gw2, gE, part1;
+  int rows, g16;
+  if (fused_bwd) {
+    // conv2 + LReLU/BN1 backward in one pass: gE, BN1 partials, dW2 slabs
+    rows = dgx_edge_mlp_fused_bwd_rows(B, N);
+    part1 = at::empty({rows, 2, C1}, d.f32);
+    Tensor slab = at::empty({rows, C2, C1}, d.f32);
+    gE = at::empty({E, C1}, d.bf16);
+    Tensor consts = at::cat({c2[2], c2[3], st2.scale}).contiguous();
+    check(dgx_edge_mlp_fused_bwd_bf16(P(PQ), 2 * C1, P<int32_t>(idx), B, N, k, C1, C2, P(st1.scale), P(st1.shift),
+                                      P(st1.mean), P(st1.invstd), slope1, nt.data_ptr(), P(dz), P<uint8_t>(arg),
+                                      P(consts), gE.data_ptr(), P(part1), P(slab), rows, d.stream),
+          "edge mlp fused bwd");
+    gw2 = at::empty({C2, C1}, d.f32);
+    check(dgx_slab_reduce_f32(P(slab), rows, C2, C1, C2, P(gw2), C1, d.stream), "dW2 slab reduce");
+    g16 = 1;
+  } else {
+    Tensor dZ2;
+    if (fused) {
+      // z2 recomputed from h1 on the MFMA, BN2 backward in the GEMM's epilogue:
+      // dZ2 = c1 z2 + c0 + [slot] a2 dz, stored bf16 (z2 never reaches HBM)
+      dZ2 = at::empty({E, C2}, d.bf16);
+      Tensor consts = at::cat({c2[2], c2[3], st2.scale}).contiguous();
+      check(dgx_gemm_dz2_bf16(H1.data_ptr(), nt.data_ptr(), (int)E, C2, C1, P(dz), P<uint8_t>(arg), P(consts), k,
+                              dZ2.data_ptr(), d.stream),
+            "edge dz2 gemm");
+    } else {
+      dZ2 = at::empty({E, C2}, Z2.options());
+      check(dgx_edge_mlp_dz_f32(P(dz), P<uint8_t>(arg), Z2.data_ptr(), (int)z16, B, N, k, C2, P(st2.scale), P(c2[2]),
+                                P(c2[3]), dZ2.data_ptr(), d.stream),
+            "edge dz2");
+    }
+    // ---- conv2 GEMMs: dH1 = dZ2 W2, dW2 = dZ2^T H1; then LReLU + BN1 backward
+    if (have_prep && z16 && C1 == 64) {
+      gw2 = at::empty({C2, C1}, d.f32);
+      // dH1 never leaves the GEMM tile: its epilogue forms g = dH1 LReLU'(z1) (bf16)
+      // and the BN1-backward column partials
+      lds_atb(d, dZ2, H1, gw2, 0, decode(opts).slab_cap_mb, nullptr);
+      rows = dgx_gemm_h1bwd_rows((int)E);
+      part1 = at::empty({rows, 2, C1}, d.f32);
+      gE = at::empty({E, C1}, d.bf16);
+      check(dgx_gemm_h1bwd_bf16(dZ2.data_ptr(), tn.data_ptr(), (int)E, C1, C2, P(PQ), 2 * C1, P<int32_t>(idx), N, k,
+                                P(st1.scale), P(st1.shift), P(st1.mean), P(st1.invstd), slope1, gE.data_ptr(),
+                                P(part1), rows, d.stream),
+            "edge h1 bwd gemm");
+      g16 = 1;
+    } else {
+      if (have_prep && z16) {
+        gE = lds_xwt(d, dZ2, tn, nullptr, false);
+        gw2 = at::empty({C2, C1}, d.f32);
+        lds_atb(d, dZ2, H1, gw2, 0, decode(opts).slab_cap_mb, nullptr);
+      } else {
+        Tensor W2 = w2.reshape({C2, C1}), dZ2f = dZ2.to(at::kFloat), H1f = H1.to(at::kFloat);
+        gE = bf16 ? mm16(d, dZ2f, W2) : mm32(d, dZ2f, W2, nullptr, false);
+        gw2 = bf16 ? mm16(d, dZ2f.t(), H1f) : mm32(d, dZ2f.t(), H1f, nullptr, false);
+      }
+      rows = dgx_edge_mlp_h1_bwd_rows(B, N, k, C1);
+      part1 = at::empty({rows, 2, C1}, d.f32);
+      check(dgx_edge_mlp_h1_bwd_f32(P(gE), P(PQ), 2 * C1, P<int32_t>(idx), B, N, k, C1, P(st1.scale), P(st1.shift),
+                                    P(st1.mean), P(st1.invstd), slope1, P(part1), rows, d.stream),
+            "edge h1 bwd");
+      g16 = 0;
+    }
+  }
+  auto c1 = backward_consts(d, part1, rows, (double)E, st1);   // dgamma1, dbeta1, e0, e1
+  // ---- dP / dQ over the graph
+  Tensor rowptr = at::empty({M + 1}, d.i32), edges = at::empty({E}, d.i32);
+  check(dgx_graph_reverse(P<int32_t>(idx), B, N, k, P<int32_t>(rowptr), P<int32_t>(edges), d.stream), "reverse graph");
+  Tensor dPQ = at::empty({M, 2 * C1}, d.f32);
+  check(dgx_edge_mlp_scatter_f32(gE.data_ptr(), g16, P(PQ), 2 * C1, P(sumP1), P<int32_t>(rowptr), P<int32_t>(edges), B,
+                                 N, k, C1, P(st1.scale), P(c1[2]), P(c1[3]), P(dPQ), d.stream),
+        "edge h1 scatter");
+  // ---- conv1 (K = C, tiny): dW1 = [dP^T X | dQ^T X], dX = dP W1a + dQ W1b
+  Tensor gw1, dx = at::empty({0}, d.f32);
+  if (bf16) {   // the engine's GEMMs (split-K over the M rows, un-stacked in the slab sum)
+    gw1 = at::empty({C1, 2 * C}, d.f32);
+    mm_atb(d, dPQ, X, gw1, C1, nullptr);
+    if (x_needs_grad) {
+      Tensor dX = at::empty({M, C}, d.f32);
+      mm_xw(d, dPQ, split_weight(w1, C, C1), dX, false);
+      dx = dX.view({B, N, C}).permute({0, 2, 1});
+    }
+  } else {
+    Tensor dwcat = mm32(d, dPQ.t(), X, nullptr, false);   // (2C1, C)
+    gw1 = at::cat({dwcat.narrow(0, 0, C1), dwcat.narrow(0, C1, C1)}, 1);
+    if (x_needs_grad) dx = mm32(d, dPQ, split_weight(w1, C, C1), nullptr, false).view({B, N, C}).permute({0, 2, 1});
+  }
+  return {dx, gw1.reshape(w1.sizes()), c1[0], c1[1], gw2.view(w2.sizes()), c2[0], c2[1]};
+}
+
+// dgx_host::bn_batch_stats -> [scale, shift, mean, invstd] of one layer (dgx.bn.batch_stats)
+std::vector<Tensor> bn_batch_stats(const Tensor& partials, int64_t rows, double count, const Tensor& gamma,
+                                   const Tensor& beta, const c10::List<std::optional<Tensor>>& bn_t_l,
+                                   std::vector<double> bn_f, std::vector<int64_t> bn_i, std::string group) {
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() &&
+                  partials.numel() >= rows * 2 * gamma.size(0),
+              "dgx bn: contiguous fp32 (rows, 2, C) partials expected");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(partials.device());
+  Dev d(partials);
+  Stats st = batch_stats(d, partials, (int)rows, count, gamma, beta, parse_bn(to_vec(bn_t_l), bn_f, bn_i, {group}, 1, 6)[0]);
+  return {st.scale, st.shift, st.mean, st.invstd};
+}
+
+// dgx_host::bn_backward_consts -> [dgamma, dbeta, c0, c1] (dgx.bn.backward_consts)
+std::vector<Tensor> bn_backward_consts(const Tensor& partials, int64_t rows, double count, const Tensor& scale,
+                                       const Tensor& mean, const Tensor& invstd, bool eval, std::string group) {
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() &&
+                  partials.numel() >= rows * 2 * scale.size(0),
+              "dgx bn: contiguous fp32 (rows, 2, C) partials expected");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(partials.device());
+  Dev d(partials);
+  auto r = backward_consts(d, partials, (int)rows, count, Stats{scale, Tensor(), mean, invstd, group, eval});
+  return {r[0], r[1], r[2], r[3]};
+}
+
 // DGCNN.forward (dgcnn.py:80-103) as one op: the EdgeConv chain + conv5 forward and,
 // from a C++ autograd node, the whole backward. Every mode (bf16 / fp32, train / eval,
 // SyncBatchNorm) runs the chain_* / pointconv_* schedule above.
@@ -1606,8 +1923,12 @@ std::vector<double> knn_timing(bool on) {
 }
 
 // dgx_host::layout(): this file's name tables (dgx.schedule holds the same ones; a test compares them)
-std::tuple<std::vector<std::string>, std::vector<std::string>, std::vector<std::string>> layout() {
-  return {{kChainNames, kChainNames + kPerLayer}, {kPcNames, kPcNames + kNumPcFields}, {kOptNames, kOptNames + kNumOptBits}};
+std::tuple<std::vector<std::string>, std::vector<std::string>, std::vector<std::string>, std::vector<std::string>>
+layout() {
+  return {{kChainNames, kChainNames + kPerLayer},
+          {kPcNames, kPcNames + kNumPcFields},
+          {kOptNames, kOptNames + kNumOptBits},
+          {kEmlpNames, kEmlpNames + kNumEmlpFields}};
 }
 
 }  // namespace
@@ -1627,7 +1948,17 @@ TORCH_LIBRARY(dgx_host, m) {
   m.def("dgcnn(Tensor x, Tensor[] params, Tensor?[] bufs, float[] bn_f, int[] bn_i, str[] groups, Tensor? idx0, "
         "int k, bool bf16, int opts) -> Tensor");
   m.def("knn_timing(bool on) -> float[]", &knn_timing);
-  m.def("layout() -> (str[] chain_fields, str[] pointconv_fields, str[] opts_bits)", &layout);
+  m.def("edge_mlp2_forward(Tensor x, Tensor idx, int k, Tensor w1, Tensor g1, Tensor b1, Tensor w2, Tensor g2, "
+        "Tensor b2, Tensor?[] bn_t, float[] bn_f, int[] bn_i, str[] groups, bool bf16, bool need_grad, "
+        "bool fused_bwd) -> (Tensor, Tensor[])");
+  m.def("edge_mlp2_backward(Tensor dout, Tensor[] saved, Tensor w1, Tensor w2, int[] shape, int k, int[] eval, "
+        "str[] groups, float[] slopes, bool bf16, bool x_needs_grad, int opts) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("bn_batch_stats(Tensor partials, int rows, float count, Tensor gamma, Tensor beta, Tensor?[] bn_t, "
+        "float[] bn_f, int[] bn_i, str group) -> Tensor[]");
+  m.def("bn_backward_consts(Tensor partials, int rows, float count, Tensor scale, Tensor mean, Tensor invstd, "
+        "bool eval, str group) -> Tensor[]");
+  m.def("layout() -> (str[] chain_fields, str[] pointconv_fields, str[] opts_bits, str[] edge_mlp_fields)", &layout);
 }
 
 TORCH_LIBRARY_IMPL(dgx_host, CompositeImplicitAutograd, m) {
@@ -1639,4 +1970,8 @@ TORCH_LIBRARY_IMPL(dgx_host, CompositeExplicitAutograd, m) {
   m.impl("chain_backward", chain_backward);
   m.impl("pointconv_forward", pointconv_forward);
   m.impl("pointconv_backward", pointconv_backward);
+  m.impl("edge_mlp2_forward", edge_mlp2_forward);
+  m.impl("edge_mlp2_backward", edge_mlp2_backward);
+  m.impl("bn_batch_stats", bn_batch_stats);
+  m.impl("bn_backward_consts", bn_backward_consts);
 }

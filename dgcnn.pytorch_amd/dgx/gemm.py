@@ -6,58 +6,11 @@ column i of a row-major (K, ld) buffer). Operands are fp32 or bf16 views of
 existing buffers (column slices of the concat buffer included): nothing is
 copied or converted on the host side.
 """
-import threading
-
 import torch
 
 from . import _native as nat
 
 EPI_STORE, EPI_ACCUM, EPI_STATS, EPI_SLAB, EPI_STATS16 = 0, 1, 2, 3, 4
-
-# Optional per-thread instrumentation (tools): when a list, every GEMM launch
-# of this thread appends (start_event, end_event, flops, tag) recorded on the
-# launch stream. Per thread, so nn.DataParallel replicas (one Python thread per
-# device) never record into each other's lists.
-_tls = threading.local()
-
-
-def set_timing(lst):
-    _tls.timing = lst
-
-
-class _Timed:
-    def __init__(self, flops):
-        self.flops = flops
-        self.timing = getattr(_tls, "timing", None)
-
-    def __enter__(self):
-        if self.timing is not None:
-            self.e0 = torch.cuda.Event(enable_timing=True)
-            self.e1 = torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if self.timing is not None:
-            self.e1.record()
-            self.timing.append((self.e0, self.e1, self.flops, getattr(_tls, "tag", None)))
-        return False
-
-
-class tag:
-    """Label the GEMM launches issued inside (this thread only)."""
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        self.prev = getattr(_tls, "tag", None)
-        _tls.tag = self.name
-        return self
-
-    def __exit__(self, *exc):
-        _tls.tag = self.prev
-        return False
-
 
 def _operand(t, ic):
     """(pointer, is_bf16, ld) of a 2-D view whose inner dim is unit-stride."""
@@ -79,7 +32,7 @@ def gemm(a, a_ic, b, b_ic, M, N, K, epi, out, partials=None, splits=1):
         if out.dim() != 2 or out.stride(1) != 1 or out.dtype != torch.float32:
             raise RuntimeError("dgx gemm: output must be a row-major fp32 2-D view")
         ldc = out.stride(0)
-    with torch.cuda.device(out.device), _Timed(2.0 * M * N * K):
+    with torch.cuda.device(out.device):
         nat.check(nat.lib().dgx_gemm_bf16(ap, abf, aic, lda, bp, bbf, bic, ldb, M, N, K, epi, splits,
                                           nat.ptr(out), ldc, nat.ptr(partials), nat.stream_of(out)), "gemm bf16")
     return out
@@ -136,7 +89,7 @@ def mm32(a, b, out=None, accumulate=False, addend=None):
     L = nat.lib()
     S = L.dgx_gemm_f32_splits(M, N, K) if (K >= 2048 and not accumulate and addend is None) else 1
     st = nat.stream_of(out)
-    with torch.cuda.device(out.device), _Timed(2.0 * M * N * K):
+    with torch.cuda.device(out.device):
         if S > 1:
             kchunk = -(-K // S)
             kchunk = -(-kchunk // 16) * 16
@@ -154,32 +107,6 @@ def mm32(a, b, out=None, accumulate=False, addend=None):
     return out
 
 
-def mm16(a, b, out=None, accumulate=False):
-    """out (M,N) (+)= a (M,K) @ b (K,N) on the bf16 MFMA GEMM (dgx_gemm_bf16:
-    fp32 or bf16 operands rounded to bf16 while staged, fp32 accumulation);
-    transposed views read in place; long reductions split-K (deterministic)."""
-    if accumulate and out is None:
-        raise RuntimeError("dgx mm16: accumulate=True needs an output to accumulate into")
-    M, K = a.shape
-    N = b.shape[1]
-    if a.stride(1) != 1 and a.stride(0) != 1:
-        a = a.contiguous()
-    if b.stride(1) != 1 and b.stride(0) != 1:
-        b = b.contiguous()
-    a_ic = a.stride(1) != 1           # (M,K) with unit stride along M: pass a^T (K,M) row-major
-    b_ic = b.stride(1) == 1           # (K,N) row-major: opB(j,k) = b[k,j] is j-contiguous
-    A = a.t() if a_ic else a
-    Bv = b if b_ic else b.t()
-    if K >= 2048 and not accumulate and out is None and a_ic and b_ic:
-        # the weight-gradient form (reduction over the B*N rows): split-K slabs
-        o = torch.empty((M, N), dtype=torch.float32, device=a.device)
-        return mm_atb(A, Bv, o)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    gemm(A, a_ic, Bv, b_ic, M, N, K, EPI_ACCUM if accumulate else EPI_STORE, out)
-    return out
-
-
 SMALLK_MAX = 16
 
 
@@ -192,7 +119,7 @@ def mm_smallk(x, w):
         x = x.contiguous()
     w = w.contiguous()
     out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _Timed(2.0 * M * N * K):
+    with torch.cuda.device(x.device):
         nat.check(nat.lib().dgx_gemm_smallk_f32(nat.f32(x), x.stride(0) if M > 1 else K, nat.f32(w), M, N, K,
                                                 nat.f32(out), N, nat.stream_of(x)), "gemm small-k")
     return out
@@ -209,7 +136,7 @@ def mm_smallk_split(x, wref, co):
     if not w.is_contiguous():
         w = w.contiguous()
     out = torch.empty((M, 2 * co), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _Timed(2.0 * M * 2 * co * K):
+    with torch.cuda.device(x.device):
         nat.check(nat.lib().dgx_gemm_smallk_split_f32(nat.f32(x), x.stride(0) if M > 1 else K, nat.f32(w), M, co, K,
                                                       nat.f32(out), 2 * co, nat.stream_of(x)), "gemm small-k")
     return out
@@ -281,7 +208,7 @@ def lds_xwt(x16, w16, out=None, stats=False, accumulate=False, addend=None, out_
         raise RuntimeError("dgx gemm: a bf16 product is only stored together with its statistics")
     epi = (EPI_STATS16 if out_bf16 else EPI_STATS) if stats else (
         EPI_ACCUM if (accumulate or addend is not None) else EPI_STORE)
-    with torch.cuda.device(out.device), _Timed(2.0 * M * N * Kw):
+    with torch.cuda.device(out.device):
         nat.check(nat.lib().dgx_gemm_lds_bf16(
             nat.ptr(x16), _bf16_2d(x16), nat.ptr(w16), _bf16_2d(w16), 0, M, N, Kw, K, epi, 1, nat.ptr(out),
             out.stride(0), nat.ptr(part), nat.ptr(addend), addend.stride(0) if addend is not None else 0,
@@ -302,7 +229,7 @@ def lds_xwt_edge_dz(x16, w16, addend, ysel, arg, st, slope):
     part = torch.empty((rows, 2, N), dtype=torch.float32, device=x16.device)
     if addend.dtype != torch.float32 or addend.stride(1) != 1:
         raise RuntimeError("dgx gemm: addend must be a row-major fp32 view")
-    with torch.cuda.device(x16.device), _Timed(2.0 * M * N * K):
+    with torch.cuda.device(x16.device):
         nat.check(L.dgx_gemm_edge_dz_bf16(
             nat.ptr(x16), _bf16_2d(x16), nat.ptr(w16), _bf16_2d(w16), M, N, K, nat.f32(addend), addend.stride(0),
             nat.f32(ysel), nat.u8(arg), nat.f32(st.scale), nat.f32(st.shift), nat.f32(st.mean), nat.f32(st.invstd),
@@ -335,9 +262,8 @@ def lds_atb(a16, b16, out, split_rows=None):
     slab = torch.empty((used, M, N), dtype=torch.float32, device=a16.device)
     with torch.cuda.device(out.device):
         st = nat.stream_of(out)
-        with _Timed(2.0 * M * N * R):
-            nat.check(L.dgx_gemm_lds_bf16(nat.ptr(a16), _bf16_2d(a16), nat.ptr(b16), _bf16_2d(b16), 1, M, N, R, R,
-                                          EPI_SLAB, S, nat.ptr(slab), N, None, None, 0, st), "gemm lds tn")
+        nat.check(L.dgx_gemm_lds_bf16(nat.ptr(a16), _bf16_2d(a16), nat.ptr(b16), _bf16_2d(b16), 1, M, N, R, R,
+                                      EPI_SLAB, S, nat.ptr(slab), N, None, None, 0, st), "gemm lds tn")
         split = M if split_rows is None else split_rows
         nat.check(L.dgx_slab_reduce_f32(nat.ptr(slab), used, M, N, split, nat.ptr(out), out.stride(0), st),
                   "slab reduce")
@@ -411,11 +337,6 @@ def prep_weights(jobs, buf=None):
             n, ctypes.addressof(W), ctypes.addressof(CO), ctypes.addressof(CI), ctypes.addressof(ST),
             ctypes.addressof(NT), ctypes.addressof(TN), nat.stream_of(jobs[0][0])), "weight prep")
     return out
-
-
-def lds_ok_nt(x, K):
-    """Whether the DMA path takes this k-contiguous operand (else the register-staged kernel)."""
-    return x.dtype == torch.bfloat16 and K % 64 == 0 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
 
 
 def edge_dz_ok(dpq16, cin):

@@ -52,21 +52,14 @@ def _empty(dev, dtype=_F32):
 
 
 class _Rec:
-    """The autograd-context surface the engine's Functions use, recorded so a
-    custom op can run a Function's forward / backward body."""
+    """The autograd-context surface dgx.ops._GraphFeature uses, recorded so the
+    graph_feature ops can run its forward / backward body."""
 
     def __init__(self):
         self.saved_tensors = ()
-        self.needs_input_grad = (True,) * 64
 
     def save_for_backward(self, *t):
         self.saved_tensors = t
-
-    def mark_non_differentiable(self, *_):
-        pass
-
-    def set_materialize_grads(self, _):
-        pass
 
 
 class _BNSpec:
@@ -83,7 +76,7 @@ class _BNSpec:
         self.momentum = None if momentum < 0 else float(momentum)
         self.eps = float(eps)
         # (mean, var, counter) outputs the finalize writes the updated statistics
-        # to (dgx.bn._update_targets); the inputs are only read
+        # to (dgx.bn.op_args passes them on); the inputs are only read
         self.stats_out = out
 
 
@@ -544,11 +537,6 @@ def dgcnn_forward(model, x):
 # same inputs, so the gradients equal the eager Function path's bit for bit.
 # Eager callers keep the Function path (no recompute); torch.compile / export
 # trace this op (dgx.edgemlp.edge_mlp2 routes here while compiling).
-def _emlp_specs(training, track, rms, rvs, nbts, momentum, eps, outs):
-    return [_BNSpec(t, tr, rm, rv, nb, mo, e, out=o)
-            for t, tr, rm, rv, nb, mo, e, o in zip(training, track, rms, rvs, nbts, momentum, eps, outs)]
-
-
 @torch.library.custom_op("dgx::edge_mlp2", mutates_args=(), device_types="cuda")
 def edge_mlp2(x: Tensor, k: int, w1: Tensor, g1: Tensor, b1: Tensor, rm1: Tensor, rv1: Tensor, nbt1: Tensor,
               w2: Tensor, g2: Tensor, b2: Tensor, rm2: Tensor, rv2: Tensor, nbt2: Tensor, training: list[bool],
@@ -556,10 +544,11 @@ def edge_mlp2(x: Tensor, k: int, w1: Tensor, g1: Tensor, b1: Tensor, rm1: Tensor
               knn_src: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
     from . import edgemlp as EM
     outs = _stat_outputs(training, track, [rm1, rm2], [rv1, rv2], [nbt1, nbt2])
-    s1, s2 = _emlp_specs(training, track, [rm1, rm2], [rv1, rv2], [nbt1, nbt2], momentum, eps, outs)
-    with prec.mode("bf16" if bf16 else "fp32"):
-        out = EM._EdgeMLP2.forward(_Rec(), x, k, s1, s2, slopes[0], slopes[1], False, knn_src, bf16, w1, g1, b1, w2,
-                                   g2, b2)
+    specs = [_BNSpec(*a, out=o) for a, o in zip(zip(training, track, [rm1, rm2], [rv1, rv2], [nbt1, nbt2], momentum,
+                                                    eps), outs)]
+    x32 = x.float()
+    out, _ = S.edge_mlp2_forward(x32, EM.knn_graph(x32, knn_src, k), k, (w1, g1, b1, w2, g2, b2),
+                                 S.bn_lists(specs, slopes), bf16, False, EM.FUSED_BWD)
     (a1, a2, a3), (c1, c2, c3) = outs
     return out, a1, a2, a3, c1, c2, c3
 
@@ -582,15 +571,13 @@ def edge_mlp2_backward(dout: Tensor, x: Tensor, k: int, w1: Tensor, g1: Tensor, 
     en = _empty(x.device, torch.int64)
     specs = [_BNSpec(u, False, rm if not u else e, rv if not u else e, en, 0.1, ep)
              for u, rm, rv, ep in zip(use_batch, (rm1, rm2), (rv1, rv2), eps)]
-    rec = _Rec()
-    rec.needs_input_grad = (x_needs_grad,) + (True,) * 63
-    with prec.mode("bf16" if bf16 else "fp32"):
-        EM._EdgeMLP2.forward(rec, x, k, specs[0], specs[1], slopes[0], slopes[1], True, knn_src, bf16, w1, g1, b1,
-                             w2, g2, b2)
-        res = EM._EdgeMLP2.backward(rec, dout)
-    dx = res[0].contiguous() if res[0] is not None else _empty(x.device)
-    gw1, dg1, db1, gw2, dg2, db2 = res[9:15]
-    return dx, gw1.contiguous(), dg1, db1, gw2.contiguous(), dg2, db2
+    bn = S.bn_lists(specs, slopes)
+    x32 = x.float()
+    _, saved = S.edge_mlp2_forward(x32, EM.knn_graph(x32, knn_src, k), k, (w1, g1, b1, w2, g2, b2), bn, bf16, True,
+                                   EM.FUSED_BWD)
+    dx, gw1, dg1, db1, gw2, dg2, db2 = S.edge_mlp2_backward(dout, saved, w1, w2, x.shape, k, bn.evals, bn.groups,
+                                                            bn.slopes, S.Decision(bf16, S.opts()), x_needs_grad)
+    return dx.contiguous(), gw1.contiguous(), dg1, db1, gw2.contiguous(), dg2, db2
 
 
 @edge_mlp2_backward.register_fake

@@ -99,22 +99,6 @@ def mode(name):
         _mode = prev
 
 
-def operand(t):
-    """GEMM operand in the current precision (bf16 copies are dense)."""
-    return t.to(torch.bfloat16) if _mode == "bf16" else t
-
-
-def mm(a, b, out=None, accumulate=False):
-    """a @ b (fp32 output) on the engine's GEMMs in the current precision:
-    fp32 MFMA (dgx.gemm.mm32) or bf16 operands with fp32 accumulation
-    (dgx.gemm.mm16). Transposed views are read in place. ``accumulate``:
-    out += a @ b."""
-    from . import gemm
-    if _mode == "bf16":
-        return gemm.mm16(a, b, out=out, accumulate=accumulate)
-    return gemm.mm32(a, b, out=out, accumulate=accumulate)
-
-
 def no_autocast(fn):
     """Run an autograd.Function's forward/backward with CUDA autocast disabled.
 

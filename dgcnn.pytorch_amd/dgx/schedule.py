@@ -1,8 +1,8 @@
 """The one Python binding of the C++ schedule (libdgx_torch.so,
 csrc/dgx_torch.cpp): every ``torch.ops.dgx_host`` call of the EdgeConv chain,
-conv5 and the one-op DGCNN goes through here, for the eager op (dgx.host), the
-autograd Functions (dgx.edgeconv, dgx.pointconv) and the torch.library ops
-(dgx.library) alike. What they share lives here once: the precision / options
+conv5, PositionEmbedding's edge MLP and the one-op DGCNN goes through here, for
+the eager op (dgx.host), the autograd Functions (dgx.edgeconv, dgx.pointconv,
+dgx.edgemlp) and the torch.library ops (dgx.library) alike. What they share lives here once: the precision / options
 decision taken at forward entry, the BatchNorm argument lists, the kNN-sharing
 lookup, and the names of the saved-state lists the schedule hands back for
 backward (``dgx_host::layout()`` returns the C++ side's tables; a test holds
@@ -21,6 +21,11 @@ from . import precision as prec
 CHAIN_FIELDS = ("idx", "PQ", "ysel", "arg", "sumP", "scale", "shift", "mean", "invstd")
 # conv5's saved list
 PC_FIELDS = ("Xop", "Z", "scale", "shift", "mean", "invstd", "nt", "tn", "xhi", "xlo")
+# the edge MLP's saved list (absent tensors are empty): conv1's operand and kNN
+# graph, PQ, sum_k P_j, h1 / z2 where the forward stored them, conv2's selected
+# value and slot, the two BN layers' per-channel state, conv2's bf16 weight copies
+EMLP_FIELDS = ("X", "idx", "PQ", "sumP", "H1", "Z2", "ysel", "arg", "scale1", "shift1", "mean1", "invstd1",
+               "scale2", "shift2", "mean2", "invstd2", "nt", "tn")
 # bit i of the opts word is the A/B switch of this name (module attributes of
 # dgx.edgeconv, documented there); bits 8-15 carry gemm.SLAB_CAP_MB
 OPT_BITS = ("SCATTER_PACKED", "FOLD_BN_BWD", "FUSE_KNN_IMAGE", "FUSE_EDGE_DZ", "SPLIT32", "SCATTER_PUSH",
@@ -28,6 +33,7 @@ OPT_BITS = ("SCATTER_PACKED", "FOLD_BN_BWD", "FUSE_KNN_IMAGE", "FUSE_EDGE_DZ", "
 
 ChainBlock = namedtuple("ChainBlock", CHAIN_FIELDS)
 PcSaved = namedtuple("PcSaved", PC_FIELDS)
+EmlpSaved = namedtuple("EmlpSaved", EMLP_FIELDS)
 Decision = namedtuple("Decision", "bf16 opts")
 BnLists = namedtuple("BnLists", "t f i groups slopes evals")
 
@@ -127,3 +133,26 @@ def pointconv_backward(dout, saved, weight, B, N, slope, ev, group, d):
 def dgcnn(x, k, params, bn, d, idx0):
     """DGCNN.forward as one op; ``bn``: bn_lists(..., targets=False) of blocks + conv5."""
     return _host().dgcnn(x, params, bn.t, bn.f, bn.i, bn.groups, idx0, k, d.bf16, d.opts)
+
+
+def edge_mlp2_forward(x, idx, k, params, bn, bf16, need_grad, fused_bwd):
+    """-> (out (B, C2, N), saved as EMLP_FIELDS); ``params``: (w1, g1, b1, w2, g2, b2),
+    ``bn``: bn_lists of the two layers, ``idx``: int32 (B, N, k) kNN graph."""
+    return _host().edge_mlp2_forward(x, idx, k, *params, bn.t, bn.f, bn.i, bn.groups, bool(bf16), bool(need_grad),
+                                     bool(fused_bwd))
+
+
+def edge_mlp2_backward(dout, saved, w1, w2, shape, k, evals, groups, slopes, d, x_needs_grad):
+    """-> (dx or empty, dW1, dgamma1, dbeta1, dW2, dgamma2, dbeta2)"""
+    return _host().edge_mlp2_backward(dout, list(saved), w1, w2, list(shape), k, evals, groups, slopes, d.bf16,
+                                      bool(x_needs_grad), d.opts)
+
+
+def bn_batch_stats(partials, rows, count, gamma, beta, bn):
+    """-> [scale, shift, mean, invstd]; ``bn``: bn_lists of the one layer."""
+    return _host().bn_batch_stats(partials, rows, float(count), gamma, beta, bn.t, bn.f, bn.i, bn.groups[0])
+
+
+def bn_backward_consts(partials, rows, count, scale, mean, invstd, ev, group):
+    """-> [dgamma, dbeta, c0, c1]"""
+    return _host().bn_backward_consts(partials, rows, float(count), scale, mean, invstd, bool(ev), group)

@@ -85,6 +85,8 @@ def test_host_op_library_loads():
         "chain_backward": "dgx_host::chain_backward(Tensor dxcat, Tensor xcat, Tensor xcat16, Tensor[] saved",
         "pointconv_forward": "dgx_host::pointconv_forward(Tensor X, Tensor X16, int B, int N",
         "pointconv_backward": "dgx_host::pointconv_backward(Tensor dout, Tensor[] saved",
+        "edge_mlp2_forward": "dgx_host::edge_mlp2_forward(Tensor x, Tensor idx, int k, Tensor w1",
+        "edge_mlp2_backward": "dgx_host::edge_mlp2_backward(Tensor dout, Tensor[] saved, Tensor w1, Tensor w2",
         "knn_timing": "dgx_host::knn_timing(bool on) -> float[]",
     }
     for name, head in want.items():
@@ -99,8 +101,8 @@ def test_schedule_layout_named_once(monkeypatch):
     A/B switch of dgx.edgeconv at the bit of its name, read at call time."""
     from dgx import edgeconv as E, gemm as G, host, schedule as S
     host.load()
-    chain, pc, bits = (tuple(names) for names in torch.ops.dgx_host.layout())
-    assert (chain, pc, bits) == (S.CHAIN_FIELDS, S.PC_FIELDS, S.OPT_BITS)
+    chain, pc, bits, emlp = (tuple(names) for names in torch.ops.dgx_host.layout())
+    assert (chain, pc, bits, emlp) == (S.CHAIN_FIELDS, S.PC_FIELDS, S.OPT_BITS, S.EMLP_FIELDS)
     assert E.opts is S.opts
     monkeypatch.setattr(G, "SLAB_CAP_MB", 0)
     for on in bits:
