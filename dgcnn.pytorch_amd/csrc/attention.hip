@@ -23,8 +23,14 @@
 // Backward: delta = rowsum(dO ∘ O) (attn_delta_kernel); dQ by a query-owned
 // pass (attn_bwd_dq_kernel: Sᵀ, dPᵀ = V dOᵀ, dSᵀ, dQᵀ += Kᵀ dSᵀ) and dK, dV by
 // a key-owned pass (attn_bwd_dkv_kernel: S = Q Kᵀ, dP = dO Vᵀ, dVᵀ += dOᵀ P,
-// dKᵀ += Qᵀ dS). No atomics: each output element is summed by one wave in a
-// fixed order, so gradients are bitwise reproducible.
+// dKᵀ += Qᵀ dS). Each output element is summed by one wave in a fixed order,
+// so gradients are bitwise reproducible. dS is packed to the 16-bit operand
+// type scaled by a power of two that follows max|dO| (at_ds_scale): the delta
+// kernel reduces the exponent of max|dO| into a few device words with an
+// integer atomic max on the float bit pattern (order-independent), both passes
+// read them, and their fp32 epilogues undo the scale exactly. The packed dS,
+// and with it the relative error of dq/dk, does not depend on the magnitude
+// of dO.
 //
 // Dropout: element (row = (b*H + h)*Nq + q, key) is kept iff
 // hash(row, key, seed) >= p * 2^32; kept weights are scaled by 1 / (1 - p).
@@ -74,7 +80,9 @@ constexpr int AT_KT = 64;        // keys per streamed K/V tile
 constexpr int AT_KW = 16;        // keys per wave, dK/dV pass
 constexpr int AT_KB = 4 * AT_KW; // keys per block, dK/dV pass
 constexpr int AT_QT = 64;        // queries per streamed Q/dO tile, dK/dV pass
-constexpr float AT_DS_SCALE = 256.f;  // dS enters its MFMA scaled by 2^8 (no fp16 subnormals), undone exactly
+constexpr int AT_DS_LOG2 = 8;    // dS enters its MFMA as dS * 2^8 / 2^floor(log2 max|dO|), undone exactly
+constexpr int AT_GMAX_WORDS = DGX_ATTN_GMAX_WORDS;  // max|dO| is reduced into this many words (one per lane to read)
+static_assert(AT_GMAX_WORDS == 64, "one word per lane of a wave");
 
 // LDS row stride in 32-bit words for a D-wide 16-bit tile: D/2 + 8 (== 8 mod 64
 // for D = 128, 40 for D = 64) puts the 8 rows x 4 column chunks of a 32-lane
@@ -148,6 +156,15 @@ __device__ __forceinline__ f32x4 mmp(const s16x8 (&a)[NP], const s16x8 (&b)[NP],
     return Mma<T>::run(a[0], b[0], c);
 }
 
+// c += a b with every plane product (lo.lo too when split): dP = dO Vᵀ, which must
+// cancel against delta = rowsum(dO ∘ O) in dS = P (dP - delta) where a row's P is
+// one-hot (O = V[target] exactly): the dropped term would stay in dS, times |q|.
+template <typename T, int NP>
+__device__ __forceinline__ f32x4 mmp_full(const s16x8 (&a)[NP], const s16x8 (&b)[NP], f32x4 c) {
+    if constexpr (NP == 2) c = Mma<T>::run(a[1], b[1], c);
+    return mmp<T, NP>(a, b, c);
+}
+
 // Register-staged copy of a [64][D] 16-bit tile (rows from `row0`, row stride
 // sN elements) into LDS: issue() loads into registers, commit() writes them.
 template <int D>
@@ -194,9 +211,9 @@ struct AtOp {
 struct AtArgs {
     AtOp q, k, v, dout;                 // dout shares O's (sB, sN, sH)
     const void* o;                      // forward output as stored (16-bit, or fp32 when split)
-    const float* dout32;                // split mode: dO in fp32 (for delta)
     int64_t osB, osN, osH;
     float *lse, *delta;
+    uint32_t* gmax;                     // [AT_GMAX_WORDS] after delta's rows: exponent bits of max|dO| (attn_delta_kernel)
     int H, Nq, Nk;
     float scale_log2;   // log2(e) * scale
     float scale;        // the softmax scale
@@ -215,6 +232,22 @@ __device__ __forceinline__ void at_seed(const AtArgs& a, uint32_t& s0, uint32_t&
     } else {
         s0 = a.s0, s1 = a.s1;
     }
+}
+
+// The dS scale of this launch and its inverse, both powers of two: with
+// e = floor(log2 max|dO|), max|dO| / 2^e lies in [1, 2) and dS is packed as
+// dS * 2^(8 - e). A non-finite max|dO| (the gradients are non-finite whatever
+// the scale) takes e = 0; a zero or tiny one is clamped so that both factors
+// stay normal numbers.
+__device__ __forceinline__ void at_ds_scale(const AtArgs& a, float& ds, float& inv) {
+    uint32_t w = a.gmax[threadIdx.x & 63];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) w = max(w, (uint32_t)__shfl_xor((int)w, o));
+    int e = (int)(__builtin_amdgcn_readfirstlane(w) >> 23);  // biased exponent; the sign bit is clear
+    if (e == 255) e = 127;
+    e = max(e, AT_DS_LOG2 + 1);
+    ds = __uint_as_float((uint32_t)(254 + AT_DS_LOG2 - e) << 23);
+    inv = __uint_as_float((uint32_t)(e - AT_DS_LOG2) << 23);
 }
 
 template <int D, int NP>
@@ -366,7 +399,13 @@ __global__ __launch_bounds__(AT_THREADS, NP == 2 ? 1 : 2) void attn_fwd_kernel(A
 }
 
 // delta[row] = sum_d dO . O (fp32), one 16-lane group per row, 16-byte loads;
-// fmt 0 f16, 1 bf16, 2 f32.
+// fmt 0 f16, 1 bf16, 2 f32 (O fp32, dO as its two bf16 planes). Also gmax[] =
+// exponent bits of the largest |dO| (zeroed by the host before the launch):
+// non-negative floats order like their bits, so an integer max serves. One
+// atomic per block at most, spread over AT_GMAX_WORDS words, and none when the
+// word already holds as much (a stale read only costs an atomic): atomics on
+// one word run at under a hundred per microsecond, a wave each would be tens
+// of thousands of them.
 __device__ __forceinline__ float h2f(uint32_t w, int hi, int fmt) {
     const uint16_t u = (uint16_t)(w >> (16 * hi));
     return fmt == 1 ? __uint_as_float((uint32_t)u << 16) : (float)__builtin_bit_cast(_Float16, u);
@@ -378,17 +417,23 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(AtArgs a, int B, int fm
     const int i = threadIdx.x & 15;
     const int64_t rows = (int64_t)B * a.H * a.Nq;
     float acc = 0.f;
+    uint32_t mx = 0u;
     if (rowg < rows) {
         const int64_t bh = rowg / a.Nq, q = rowg - bh * a.Nq;
         const int b = (int)(bh / a.H), h = (int)(bh - (int64_t)b * a.H);
         const int64_t off = b * a.osB + h * a.osH + q * a.osN;
-        if (fmt == 2) {  // fp32: 4 per load
+        if (fmt == 2) {  // fp32 O, 4 per load; dO = hi + lo from its planes, the value dP = dO Vᵀ is formed from
             const float* op = static_cast<const float*>(a.o) + off;
-            const float* gp = a.dout32 + off;
+            const uint16_t* gp = a.dout.p + off;
             for (int d = 4 * i; d < D; d += 64) {
                 const float4 x = *reinterpret_cast<const float4*>(op + d);
-                const float4 y = *reinterpret_cast<const float4*>(gp + d);
-                acc = fmaf(x.x, y.x, fmaf(x.y, y.y, fmaf(x.z, y.z, fmaf(x.w, y.w, acc))));
+                const uint2 yh = *reinterpret_cast<const uint2*>(gp + d);
+                const uint2 yl = *reinterpret_cast<const uint2*>(gp + a.dout.sP + d);
+                const float yv[4] = {h2f(yh.x, 0, 1) + h2f(yl.x, 0, 1), h2f(yh.x, 1, 1) + h2f(yl.x, 1, 1),
+                                     h2f(yh.y, 0, 1) + h2f(yl.y, 0, 1), h2f(yh.y, 1, 1) + h2f(yl.y, 1, 1)};
+                acc = fmaf(x.x, yv[0], fmaf(x.y, yv[1], fmaf(x.z, yv[2], fmaf(x.w, yv[3], acc))));
+#pragma unroll
+                for (int u = 0; u < 4; ++u) mx = max(mx, __float_as_uint(yv[u]) & 0x7fffffffu);
             }
         } else {  // 16-bit: 8 per load
             const uint16_t* op = static_cast<const uint16_t*>(a.o) + off;
@@ -398,14 +443,28 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(AtArgs a, int B, int fm
                 const uint4 y = *reinterpret_cast<const uint4*>(gp + d);
                 const uint32_t xw[4] = {x.x, x.y, x.z, x.w}, yw[4] = {y.x, y.y, y.z, y.w};
 #pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    acc = fmaf(h2f(xw[u], 0, fmt), h2f(yw[u], 0, fmt), fmaf(h2f(xw[u], 1, fmt), h2f(yw[u], 1, fmt), acc));
+                for (int u = 0; u < 4; ++u) {
+                    const float g0 = h2f(yw[u], 0, fmt), g1 = h2f(yw[u], 1, fmt);
+                    acc = fmaf(h2f(xw[u], 0, fmt), g0, fmaf(h2f(xw[u], 1, fmt), g1, acc));
+                    mx = max(mx, max(__float_as_uint(g0) & 0x7fffffffu, __float_as_uint(g1) & 0x7fffffffu));
+                }
             }
         }
     }
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 16);
     if (rowg < rows && i == 0) a.delta[rowg] = acc;
+    __shared__ uint32_t wmx[4];
+    mx &= 0x7f800000u;  // only the exponent is used
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+    if ((threadIdx.x & 63) == 0) wmx[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mx = max(max(wmx[0], wmx[1]), max(wmx[2], wmx[3]));
+        uint32_t* w = a.gmax + (blockIdx.x & (AT_GMAX_WORDS - 1));
+        if (mx > __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(w, mx);
+    }
 }
 
 // ------------------------------------------------------------- backward dQ --
@@ -414,6 +473,8 @@ __global__ __launch_bounds__(AT_THREADS, (D == 128 || NP == 2) ? 1 : 2) void att
     AtArgs a, float* __restrict__ dq, int64_t dsB, int64_t dsN, int64_t dsH) {
     uint32_t sd0, sd1;
     at_seed(a, sd0, sd1);
+    float dsc, dsi;
+    at_ds_scale(a, dsc, dsi);
     constexpr int RSW = at_rsw<D>();
     constexpr int KS = D / 32, DB = D / 16, TW = 64 * RSW;
     extern __shared__ __attribute__((aligned(16))) uint32_t at_lds[];
@@ -488,10 +549,10 @@ __global__ __launch_bounds__(AT_THREADS, (D == 128 || NP == 2) ? 1 : 2) void att
 #pragma unroll
                 for (int qt = 0; qt < 2; ++qt) {
                     s[qt][kt] = mmp<T, NP>(kf, qf[qt][ks], s[qt][kt]);
-                    dp[qt][kt] = mmp<T, NP>(vf, gf[qt][ks], dp[qt][kt]);
+                    dp[qt][kt] = mmp_full<T, NP>(vf, gf[qt][ks], dp[qt][kt]);
                 }
             }
-        // dSᵀ = P (dP (keep / (1-p)) - delta), scaled by 2^8 for the MFMA
+        // dSᵀ = P (dP (keep / (1-p)) - delta), scaled by dsc for the MFMA
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
             const uint32_t row = row0 + 16 * qt + c;
@@ -503,7 +564,7 @@ __global__ __launch_bounds__(AT_THREADS, (D == 128 || NP == 2) ? 1 : 2) void att
                     const float p = key < a.Nk ? __builtin_amdgcn_exp2f(s[qt][kt][r] * a.scale_log2 - lse[qt]) : 0.f;
                     float d = dp[qt][kt][r];
                     if constexpr (DROP) d = at_keep(row, (uint32_t)key, a.p32, sd0, sd1) ? d * a.rdrop : 0.f;
-                    s[qt][kt][r] = p * (d - dl[qt]) * AT_DS_SCALE;
+                    s[qt][kt][r] = p * ((d - dl[qt]) * dsc);
                 }
         }
         // dQᵀ += Kᵀ dSᵀ
@@ -522,7 +583,7 @@ __global__ __launch_bounds__(AT_THREADS, (D == 128 || NP == 2) ? 1 : 2) void att
             }
         }
     }
-    const float f = a.scale / AT_DS_SCALE;
+    const float f = a.scale * dsi;
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         const int q = q0 + 16 * qt + c;
@@ -543,6 +604,8 @@ __global__ __launch_bounds__(AT_THREADS, NP == 2 ? 1 : 2) void attn_bwd_dkv_kern
     int64_t vsN, int64_t vsH) {
     uint32_t sd0, sd1;
     at_seed(a, sd0, sd1);
+    float dsc, dsi;
+    at_ds_scale(a, dsc, dsi);
     constexpr int RSW = at_rsw<D>();
     constexpr int KS = D / 32, DB = D / 16, TW = 64 * RSW;
     extern __shared__ __attribute__((aligned(16))) uint32_t at_lds[];
@@ -615,7 +678,7 @@ __global__ __launch_bounds__(AT_THREADS, NP == 2 ? 1 : 2) void attn_bwd_dkv_kern
                     ga[pl] = lds_row8<RSW>(gl + pl * TW, 16 * qt + c, 32 * ks + 8 * g);
                 }
                 s[qt] = mmp<T, NP>(qa, kf[ks], s[qt]);
-                dp[qt] = mmp<T, NP>(ga, vf[ks], dp[qt]);
+                dp[qt] = mmp_full<T, NP>(ga, vf[ks], dp[qt]);
             }
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt)
@@ -630,7 +693,7 @@ __global__ __launch_bounds__(AT_THREADS, NP == 2 ? 1 : 2) void attn_bwd_dkv_kern
                     d = kp ? d * a.rdrop : 0.f;
                     pd = kp ? p : 0.f;
                 }
-                dp[qt][r] = p * (d - dll[qi]) * AT_DS_SCALE;  // dS
+                dp[qt][r] = p * ((d - dll[qi]) * dsc);  // dS
                 s[qt][r] = pd;                                // P with the dropout mask (1/(1-p) at the end)
             }
         // dVᵀ += dOᵀ P, dKᵀ += Qᵀ dS over two 32-query steps
@@ -653,7 +716,7 @@ __global__ __launch_bounds__(AT_THREADS, NP == 2 ? 1 : 2) void attn_bwd_dkv_kern
         }
     }
     if (kvalid) {
-        const float fk = a.scale / AT_DS_SCALE, fv = DROP ? a.rdrop : 1.f;
+        const float fk = a.scale * dsi, fv = DROP ? a.rdrop : 1.f;
         float* kp = dk + b * ksB + h * ksH + (int64_t)key * ksN;
         float* vp = dv + b * vsB + h * vsH + (int64_t)key * vsN;
 #pragma unroll
@@ -753,7 +816,7 @@ int dgx_attn_fwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN
 int dgx_attn_bwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN, int64_t qsH, const void* k,
                  int64_t ksP, int64_t ksB, int64_t ksN, int64_t ksH, const void* v, int64_t vsP, int64_t vsB,
                  int64_t vsN, int64_t vsH, const void* o, const void* dout, int64_t gsP, int64_t osB, int64_t osN,
-                 int64_t osH, const float* dout32, const float* lse, float* delta, int B, int H, int Nq, int Nk, int D,
+                 int64_t osH, const float* lse, float* delta, int B, int H, int Nq, int Nk, int D,
                  float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dq, int64_t dqsB,
                  int64_t dqsN, int64_t dqsH,
                  float* dk, int64_t dksB, int64_t dksN, int64_t dksH, float* dv, int64_t dvsB, int64_t dvsN,
@@ -762,7 +825,6 @@ int dgx_attn_bwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN
         return DGX_EINVAL;
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return DGX_EINVAL;
     if (dtype < 0 || dtype > 2 || (D != 64 && D != 128)) return DGX_EUNSUPPORTED;
-    if (dtype == 2 && !dout32) return DGX_EINVAL;
     if (!op_ok(q, qsP, qsB, qsN, qsH) || !op_ok(k, ksP, ksB, ksN, ksH) || !op_ok(v, vsP, vsB, vsN, vsH) ||
         !op_ok(dout, gsP, osB, osN, osH) || (reinterpret_cast<uintptr_t>(o) & 15) != 0)
         return DGX_EINVAL;
@@ -776,7 +838,7 @@ int dgx_attn_bwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN
     a.k = AtOp{static_cast<const uint16_t*>(k), ksP, ksB, ksN, ksH};
     a.v = AtOp{static_cast<const uint16_t*>(v), vsP, vsB, vsN, vsH};
     a.dout = AtOp{static_cast<const uint16_t*>(dout), gsP, osB, osN, osH};
-    a.o = o, a.dout32 = dout32;
+    a.o = o;
     a.osB = osB, a.osN = osN, a.osH = osH;
     a.lse = const_cast<float*>(lse), a.delta = delta, a.H = H, a.Nq = Nq, a.Nk = Nk;
     a.scale_log2 = scale * 1.4426950408889634f, a.scale = scale;
@@ -784,6 +846,8 @@ int dgx_attn_bwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN
     a.seedp = seed_dev;
     hipStream_t st = dgx_stream(stream);
     const int64_t rows = (int64_t)B * H * Nq;
+    a.gmax = reinterpret_cast<uint32_t*>(delta + rows);
+    if (hipMemsetAsync(a.gmax, 0, AT_GMAX_WORDS * sizeof(uint32_t), st) != hipSuccess) return DGX_ELAUNCH;
     const unsigned dblocks = (unsigned)((rows * 16 + 255) / 256);
     if (D == 128) hipLaunchKernelGGL((attn_delta_kernel<128>), dim3(dblocks), dim3(256), 0, st, a, B, dtype);
     else hipLaunchKernelGGL((attn_delta_kernel<64>), dim3(dblocks), dim3(256), 0, st, a, B, dtype);

@@ -119,7 +119,7 @@ _SIGS = {
     "dgx_attn_fwd": [_i32] + [_vp, _i64, _i64, _i64, _i64] * 3 + [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32,
                                                                    _i32, _i32, _f32, _f32, ctypes.c_uint64, _vp,
                                                                    _vp],
-    "dgx_attn_bwd": [_i32] + [_vp, _i64, _i64, _i64, _i64] * 3 + [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+    "dgx_attn_bwd": [_i32] + [_vp, _i64, _i64, _i64, _i64] * 3 + [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp,
                                                                    _i32, _i32, _i32, _i32, _i32, _f32, _f32,
                                                                    ctypes.c_uint64, _vp]
                     + [_vp, _i64, _i64, _i64] * 3 + [_vp],

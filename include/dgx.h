@@ -583,15 +583,24 @@ int dgx_attn_fwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN
                  int64_t vsN, int64_t vsH, void* o, int64_t osB, int64_t osN, int64_t osH, float* lse, int B, int H,
                  int Nq, int Nk, int D, float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev,
                  void* stream);
+#define DGX_ATTN_GMAX_WORDS 64 /* words of dgx_attn_bwd's scratch after its B*H*Nq deltas */
 /* Gradients of dgx_attn_fwd (same operands, seed and p). dout: dO in the
- * operand format (planes at +gsP for dtype 2) with O's (sB, sN, sH); dout32:
- * dO in fp32 (dtype 2 only, for delta = rowsum(dO . O)); dq/dk/dv fp32 with
- * their own strides; delta: (B*H*Nq) fp32 scratch. No atomics (bitwise
- * reproducible). */
+ * operand format (planes at +gsP for dtype 2) with O's (sB, sN, sH).
+ * delta = rowsum(dO . O) is formed from that same dO (hi + lo for dtype 2) and
+ * dP = dO V^T keeps every plane product, so the two cancel in dS = P (dP -
+ * delta) where a row's weights are one-hot. dq/dk/dv fp32 with their own
+ * strides. delta: (B*H*Nq + DGX_ATTN_GMAX_WORDS) fp32 scratch: delta per row,
+ * then the words into which the exponent of max|dO| is reduced on the device
+ * (an integer atomic max on the float bit pattern: order-independent). dS is packed to the 16-bit operand type
+ * scaled by 2^8 / 2^floor(log2 max|dO|) and the scale is undone exactly in
+ * fp32, so the relative error of dq/dk does not depend on the magnitude of dO,
+ * and a dO whose true gradients fit the output type gives finite gradients.
+ * No host synchronisation; every output element is summed in a fixed order
+ * (bitwise reproducible). */
 int dgx_attn_bwd(int dtype, const void* q, int64_t qsP, int64_t qsB, int64_t qsN, int64_t qsH, const void* k,
                  int64_t ksP, int64_t ksB, int64_t ksN, int64_t ksH, const void* v, int64_t vsP, int64_t vsB,
                  int64_t vsN, int64_t vsH, const void* o, const void* dout, int64_t gsP, int64_t osB, int64_t osN,
-                 int64_t osH, const float* dout32, const float* lse, float* delta, int B, int H, int Nq, int Nk, int D,
+                 int64_t osH, const float* lse, float* delta, int B, int H, int Nq, int Nk, int D,
                  float scale, float dropout_p, uint64_t seed, const uint64_t* seed_dev, float* dq, int64_t dqsB,
                  int64_t dqsN, int64_t dqsH,
                  float* dk, int64_t dksB, int64_t dksN, int64_t dksH, float* dv, int64_t dvsB, int64_t dvsN,
