@@ -747,6 +747,19 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
   const int n = (int)L.size();
   int64_t total = 0;
   for (auto& ly : L) total += ly.co;
+  if (need_grad && !o.push) {
+    // the backward's pull scatter stages a cloud's one-channel slices in LDS: a
+    // cloud it cannot take is refused here, before the forward has run
+    // (the push form, o.push, has its own geometry and refuses in the backward).
+    // One block stands for all: the scatter doubles its point parts until the
+    // slice fits or parts * 64 >= N, an end state the channel count does not change.
+    const int pk = (bf16 || o.split32) && o.packed;
+    if (!L.empty())
+      TORCH_CHECK(dgx_edge_bwd_scatter_fits(B, N, L[0].co, pk),
+                  "dgx chain: the EdgeConv backward takes at most N = ", dgx_edge_bwd_scatter_max_n(B, L[0].co, pk),
+                  " points per cloud (B = ", B, ", ", pk ? "packed dz" : "dz + slot bytes", "), got N = ", N,
+                  "; larger clouds run forward-only (torch.no_grad)");
+  }
   ChainOut r;
   r.xcat = at::empty({M, total}, d.f32);
   Tensor xcat16 = bf16 ? at::empty({M, total}, d.bf16) : Tensor();

@@ -1704,6 +1704,29 @@ int dgx_graph_reverse(const int32_t* idx, int B, int N, int k, int32_t* rowptr, 
 }
 
 namespace {
+// slice channels of the pull scatter: 9 (8 packed) bytes per (point, channel) within BW_LDS_BYTES
+inline int scatter_slice_channels(int N, bool packed) {
+    const size_t per_pc = packed ? 8 : 9;
+    int cs = 8;
+    while (cs > 1 && per_pc * N * cs > (size_t)BW_LDS_BYTES) cs >>= 1;
+    return cs;
+}
+
+// point parts of the pull scatter: point_parts, doubled while the slice does not fit the CU's LDS
+inline int scatter_parts(int B, int slices, int N, int cs, bool packed) {
+    int parts = point_parts(B, slices, N);
+    while (scatter_lds_bytes(N, cs, parts, packed) > (size_t)160 * 1024 && parts * 64 < N) parts *= 2;
+    return parts;
+}
+
+// launch_scatter's own shape test, without a launch
+inline bool scatter_fits(int B, int N, int Co, bool packed) {
+    if (N < 1 || N > 65535) return false;
+    const int cs = scatter_slice_channels(N, packed);
+    const int parts = scatter_parts(B, (Co + cs - 1) / cs, N, cs, packed);
+    return scatter_lds_bytes(N, cs, parts, packed) <= (size_t)160 * 1024;
+}
+
 int launch_scatter(const float* PQ, int ldpq, const int32_t* rowptr, const int32_t* edges, const float* dz,
                    const uint8_t* arg, const float* sumP, int B, int N, int k, int Co, const float* scale,
                    const float* c0, const float* c1, void* dPQ, int out_bf16, bool packed, void* stream,
@@ -1716,9 +1739,7 @@ int launch_scatter(const float* PQ, int ldpq, const int32_t* rowptr, const int32
     if (N > 65535) return DGX_EUNSUPPORTED;
     // slice channels: 9 (8 packed) bytes per (point, channel) within BW_LDS_BYTES
     // (16 measured slower: one workgroup per CU; 4 slower: per-edge work over fewer channels)
-    const size_t per_pc = packed ? 8 : 9;
-    int cs = 8;
-    while (cs > 1 && per_pc * N * cs > (size_t)BW_LDS_BYTES) cs >>= 1;
+    int cs = scatter_slice_channels(N, packed);
     // LDS-staged in-edge ids (16-bit words: N <= 1024, packed dz words): at most
     // SCATTER_IDL_CS channels per slice so the slices, the ids (capacity 1.75x a
     // part's mean in-edge count; a part beyond it reads its ids from HBM) and
@@ -1734,11 +1755,10 @@ int launch_scatter(const float* PQ, int ldpq, const int32_t* rowptr, const int32
     const bool idl = SCATTER_IDL_CS > 0 && packed && N <= 1024 && k <= 64;
     if (idl) cs = std::min(cs, SCATTER_IDL_CS);
     const int slices = (Co + cs - 1) / cs;
-    int parts = point_parts(B, slices, N);
     // a cloud whose one-channel slices exceed BW_LDS_BYTES (N > 9216) takes up to
     // the CU's 160 KiB (one workgroup per CU; more point parts shrink the order
-    // array): N <= 20000 packed, 17900 unpacked
-    while (scatter_lds_bytes(N, cs, parts, packed) > (size_t)160 * 1024 && parts * 64 < N) parts *= 2;
+    // array): N <= 20000 packed, 17900 unpacked (dgx_edge_bwd_scatter_max_n)
+    const int parts = scatter_parts(B, slices, N, cs, packed);
     int idcap = 0;
     if (idl) {
         const int per = (N + parts - 1) / parts;
@@ -1881,6 +1901,24 @@ int launch_push(const float* PQ, int ldpq, const int32_t* idx, const int32_t* ro
     return hipGetLastError() == hipSuccess ? DGX_OK : DGX_ELAUNCH;
 }
 }  // namespace
+
+int dgx_edge_bwd_scatter_fits(int B, int N, int Co, int packed) {
+    return B >= 1 && Co >= 1 && scatter_fits(B, N, Co, packed != 0) ? 1 : 0;
+}
+
+int dgx_edge_bwd_scatter_max_n(int B, int Co, int packed) {
+    if (B < 1 || Co < 1) return 0;
+    // The LDS need grows by 8 (9 unpacked) bytes per point except where one
+    // more point part becomes possible (parts * 64 < N, at N = 64 * 2^m + 1),
+    // which halves the order array: at most 2 * 64 = 128 bytes back, made up
+    // within 16 points. So the largest fitting N is searched from above, and
+    // every smaller N fits too unless the limit falls within 16 points of such
+    // a boundary (8193, 16385, 32769); with the 160 KiB of this chip it is
+    // about 17900 / 20200, far from them.
+    for (int N = 65535; N >= 1; --N)
+        if (scatter_fits(B, N, Co, packed != 0)) return N;
+    return 0;
+}
 
 int dgx_edge_bwd_scatter_f32(const float* PQ, int ldpq, const int32_t* rowptr, const int32_t* edges,
                              const float* dz, const uint8_t* arg, const float* sumP, int B, int N, int k, int Co,

@@ -1140,6 +1140,11 @@ inline int knn_qg(int nstep, int kb, int N) {
 // waves instead (knn_split_kernel, r05a/b) measured slower at every C.
 inline bool knn_small(int B, int N) { return (int64_t)B * ((N + KQ_QPB - 1) / KQ_QPB) < 512; }
 
+// query groups per wave of the kernel launch_knn launches for B clouds (dgx_knn_query_groups)
+inline int knn_groups_launched(int nstep, int kb, int B, int N) {
+    return kb <= 40 && nstep >= 16 && knn_qg(nstep, kb, N) == 2 && !knn_small(B, N) ? 2 : 1;
+}
+
 template <int NSTEP, int KB, int QG>
 int launch_knn_qg(const float* xx, int B, int N, int k, int64_t* idx64, int32_t* idx32, float* vals,
                   const float* img, const float* xximg, hipStream_t st) {
@@ -1160,7 +1165,7 @@ int launch_knn(const float* x, int64_t sB, int64_t sC, int64_t sN, const float* 
     // two query groups per wave where the MFMA chain dominates (C > 64, k <= 40:
     // the lists of two groups fit in registers); one where the selection does
     if constexpr (KB <= 40 && NSTEP >= 16) {
-        if (knn_qg(NSTEP, KB, N) == 2 && !knn_small(B, N))
+        if (knn_groups_launched(NSTEP, KB, B, N) == 2)
             return launch_knn_qg<NSTEP, KB, 2>(xx, B, N, k, idx64, idx32, vals, img, xximg, st);
     }
     return launch_knn_qg<NSTEP, KB, 1>(xx, B, N, k, idx64, idx32, vals, img, xximg, st);
@@ -1210,6 +1215,12 @@ const char* dgx_knn_kernel_name(int C, int k, int N) {
     const int b = k <= 16 ? 0 : k <= 20 ? 1 : k <= 32 ? 2 : k <= 40 ? 3 : 4;
     static const int KBS[5] = {16, 20, 32, 40, 64};
     return names.s[a][b][knn_qg(ns, KBS[b], N) - 1];
+}
+
+int dgx_knn_query_groups(int B, int C, int k, int N) {
+    if (B < 1 || C < 1 || C > 128 || k < 1 || k > 64 || N < 1) return 0;
+    const int kb = k <= 16 ? 16 : k <= 20 ? 20 : k <= 32 ? 32 : k <= 40 ? 40 : 64;   // dispatch_k's tiers
+    return knn_groups_launched(knn_nstep(C), kb, B, N);
 }
 
 int dgx_bn_lrelu_apply_knn_image_f32(const float* ysel, int B, int N, int Co, const float* scale,

@@ -30,6 +30,7 @@ _SIGS = {
     "dgx_knn_workspace_bytes": [_i32, _i32, _i32],
     "dgx_knn_image_bytes": [_i32, _i32, _i32],
     "dgx_knn_kernel_name": [_i32, _i32, _i32],
+    "dgx_knn_query_groups": [_i32, _i32, _i32, _i32],
     "dgx_bn_lrelu_apply_knn_image_f32": [_vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _vp, _sz, _vp],
     "dgx_knn_prepare_f32": [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp],
     "dgx_knn_f32": [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp],
@@ -46,6 +47,8 @@ _SIGS = {
                           _i32, _vp, _vp, _vp],
     "dgx_amp_unscale_f32": [_i32, _vp, _vp, _vp, _vp, _vp],
     "dgx_edge_partials_rows": [_i32, _i32, _i32],
+    "dgx_edge_bwd_scatter_max_n": [_i32, _i32, _i32],
+    "dgx_edge_bwd_scatter_fits": [_i32, _i32, _i32, _i32],
     "dgx_edge_fwd_gather_f32": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "dgx_edge_fwd_eval_f32": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _i32, _vp],
     "dgx_bn_finalize_f32": [_vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -70,6 +70,11 @@ size_t dgx_knn_image_bytes(int B, int C, int N);
  * rocprofv3 prints it (host-side query; lets profiles be matched to the
  * kernels that actually ran). "" for unsupported (C, k, N). */
 const char* dgx_knn_kernel_name(int C, int k, int N);
+/* Host-side: the query groups per wave (the kernel name's last template
+ * argument) that dgx_knn_select_f32 really launches for B clouds: a grid of
+ * fewer than 512 workgroups keeps one group whatever dgx_knn_kernel_name says.
+ * 0 for unsupported (C, k, N) or B < 1. */
+int dgx_knn_query_groups(int B, int C, int k, int N);
 /* dgx_bn_lrelu_apply_f32 for an EdgeConv block whose output feeds the next
  * block's kNN (dgcnn.py:84-98, the feature-space knn of x_l): writes
  * out = LeakyReLU(scale*ysel + shift) (+ its bf16 twin) AND the next kNN's
@@ -256,6 +261,14 @@ int dgx_edge_bwd_scatter_f32(const float* PQ, int ldpq, const int32_t* rowptr,
                              int k, int Co, const float* scale, const float* c0,
                              const float* c1, void* dPQ, int out_bf16,
                              void* stream);
+/* Host-only: the largest N (points per cloud) the pull scatters above and
+ * below take for B clouds of Co channels (packed != 0: packed dz|slot words).
+ * A cloud's one-channel slices must fit the CU's 160 KiB of LDS: about 17900
+ * points with slot bytes, 20000 packed; a larger N returns DGX_EUNSUPPORTED
+ * before any launch. 0 for B < 1 or Co < 1. */
+int dgx_edge_bwd_scatter_max_n(int B, int Co, int packed);
+/* Host-only, O(1): 1 when the pull scatters take this shape, else 0. */
+int dgx_edge_bwd_scatter_fits(int B, int N, int Co, int packed);
 /* dgx_bn_bwd_finalize_f32 + dgx_edge_bwd_scatter_f32 in ONE launch: every
  * workgroup reduces the dz pass's partial rows (nrows x 2 x Co) for its own
  * channels in a fixed order (fp64) and the channel slice's first workgroup

@@ -10,6 +10,10 @@ which tests/conftest.py load_golden reads under the .npz name)
   knn_cases.npz      reference knn (dgcnn.py:6-12) on synthetic clouds, C in
                      {3,9,64,128}, both memory layouts, plus a duplicate-point
                      tie set; indices in canonical order + selected pd values.
+  knn_channels.npz   reference knn on one small cloud (B 1, N 48-64, k 8) per
+                     channel width C in KNN_CHANNELS, both layouts: every kNN
+                     tier and every tail of the |x|^2 summation order. Written
+                     alone by `make_goldens.py knn_channels`.
   graph_feature.npz  get_graph_feature (dgcnn.py:15-44), all three modes.
   edgeconv_block.npz one block: get_graph_feature -> conv/BN/LReLU -> max (train
                      BN, gamma with negative entries): out, dx, dW, dgamma,
@@ -126,6 +130,30 @@ def knn_cases():
     ci, cv = canonical(idx, ref_pd(x))
     out["ties_perm_x"], out["ties_perm_idx"], out["ties_perm_val"] = pts, ci.astype(np.int32), cv
     save_npz("knn_cases.npz", **out)
+
+
+_spec = importlib.util.spec_from_file_location("dgx_test_shapes", os.path.join(REPO, "tests", "_shapes.py"))
+_shapes = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_shapes)
+KNN_CHANNELS = _shapes.KNN_CHANNELS   # one definition for the fixture and its readers
+
+
+def knn_channel_cases():
+    """One small cloud per channel width: every tier of the kNN kernels and every
+    tail (C % 4, C % 8, C % 16) of the reference's |x|^2 summation, both layouts."""
+    out = {}
+    for C in KNN_CHANNELS:
+        N, k = 48 + C % 17, 8   # 48..64, ragged against the 16- and 32-point tiles
+        pts = synth.relu_normal(700 + C, (1, N, C))
+        for layout in ("bcn", "perm"):
+            t = torch.from_numpy(pts)
+            x = t.permute(0, 2, 1) if layout == "perm" else t.permute(0, 2, 1).contiguous()
+            ci, cv = canonical(ref_knn(x, k), ref_pd(x))
+            key = f"c{C}_{layout}"
+            out[key + "_x"] = pts
+            out[key + "_idx"] = ci.astype(np.int32)
+            out[key + "_val"] = cv
+    save_npz("knn_channels.npz", **out)
 
 
 def graph_feature_cases():
@@ -288,7 +316,11 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["partseg"]:
         partseg_case()
         sys.exit(0)
+    if sys.argv[1:] == ["knn_channels"]:
+        knn_channel_cases()
+        sys.exit(0)
     knn_cases()
+    knn_channel_cases()
     graph_feature_cases()
     edgeconv_block_case()
     dgcnn_case()

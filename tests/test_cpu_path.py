@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from _shapes import KNN_CHANNELS
 from conftest import assert_knn_equivalent, load_golden, rel_err
 
 KNN_CASES = ["c3", "c9", "c64", "c128", "c3k40", "c64k32", "c3n1000"]
@@ -29,6 +30,21 @@ def test_cpu_knn_matches_reference_golden(case, layout):
     idx = knn(_cpu_view(g[key + "_x"], layout), g[key + "_idx"].shape[-1])
     assert idx.dtype == torch.int64 and idx.device.type == "cpu"
     np.testing.assert_array_equal(idx.numpy(), g[key + "_idx"])
+
+
+@pytest.mark.parametrize("layout", ["bcn", "perm"])
+@pytest.mark.parametrize("C", KNN_CHANNELS)
+def test_cpu_knn_matches_reference_every_channel_tier(C, layout):
+    """The host path against the reference at every channel width of
+    knn_channels.npz: the values of the chosen ids bit-exact, ids canonical."""
+    import oracle
+    from models.dgcnn import knn
+    g = load_golden("knn_channels.npz")
+    key = f"c{C}_{layout}"
+    x = _cpu_view(g[key + "_x"], layout)
+    idx = knn(x, g[key + "_idx"].shape[-1]).numpy()
+    pd = oracle.pairwise(x)   # test-side checker: values of the chosen ids
+    assert_knn_equivalent(idx, np.take_along_axis(pd, idx, 2), g[key + "_idx"], g[key + "_val"])
 
 
 def test_cpu_knn_ties_golden():

@@ -72,9 +72,31 @@ def test_edgeconv_block_golden(golden, cuda):
 def test_edgeconv_block_routed(cuda, C, Co, N, k):
     """Strict 1e-3 parity of outputs AND all gradients against the fp64 oracle
     that follows the engine's routing decisions (ragged N, negative gammas)."""
+    _block_routed(cuda, 2, C, Co, N, k, TOL)
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+@pytest.mark.parametrize("C,Co,N,k", [(3, 8, 8193, 8), (3, 8, 16385, 8)])
+def test_edgeconv_block_routed_large_n(cuda, C, Co, N, k, mode):
+    """One cloud past the last two slice boundaries of the forward gather (one
+    channel per LDS slice above N = 8192, more than 64 KiB of LDS per slice above
+    16384; the backward scatter in its 160 KiB mode at both) through the whole
+    block, forward and backward: 1e-3 in fp32, SURVEY §8(c)'s 2e-2 in the bf16
+    mode, and the block's kNN (generic kernel above N = 12288) equal to the
+    oracle's."""
+    from dgx import precision
+    precision.set(mode)
+    try:
+        x, idx = _block_routed(cuda, 1, C, Co, N, k, TOL if mode == "fp32" else 2e-2,
+                               dec_tol=1e-5 if mode == "fp32" else 2e-3)
+    finally:
+        precision.set("fp32")
+    np.testing.assert_array_equal(idx.view(1, N, k).cpu().numpy(), oracle.knn(x, k))
+
+
+def _block_routed(cuda, B, C, Co, N, k, tol, dec_tol=1e-5):
     from dgx.edgeconv import edgeconv_stack
     torch.manual_seed(C + Co + N)
-    B = 2
     x = torch.randn(B, C, N)
     w = (torch.randn(Co, 2 * C, 1, 1) / (2 * C) ** 0.5).numpy()
     gamma, beta = torch.randn(Co).numpy(), (0.1 * torch.randn(Co)).numpy()
@@ -92,15 +114,16 @@ def test_edgeconv_block_routed(cuda, C, Co, N, k):
     bn = {"weight": gc, "bias": bc, "running_mean": torch.zeros(Co, dtype=torch.float64),
           "running_var": torch.ones(Co, dtype=torch.float64)}
     ref, z64 = R.edgeconv_block_routed(xc, wc, bn, idx.cpu().long(), arg.cpu(), zpos.cpu())
-    check_decisions(z64, arg, zpos, B, N)
+    check_decisions(z64, arg, zpos, B, N, dec_tol)
     ref.backward(gout.double())
-    assert rel_err(out.detach().cpu(), ref.detach()) < TOL
-    assert rel_err(xg.grad.cpu(), xc.grad) < TOL
-    assert rel_err(blk[0].weight.grad.cpu(), wc.grad) < TOL
-    assert rel_err(blk[1].weight.grad.cpu(), gc.grad) < TOL
-    assert rel_err(blk[1].bias.grad.cpu(), bc.grad) < TOL
+    assert rel_err(out.detach().cpu(), ref.detach()) < tol
+    assert rel_err(xg.grad.cpu(), xc.grad) < tol
+    assert rel_err(blk[0].weight.grad.cpu(), wc.grad) < tol
+    assert rel_err(blk[1].weight.grad.cpu(), gc.grad) < tol
+    assert rel_err(blk[1].bias.grad.cpu(), bc.grad) < tol
     assert rel_err(blk[1].running_mean.cpu(), bn["running_mean"]) < 1e-5
     assert rel_err(blk[1].running_var.cpu(), bn["running_var"]) < 1e-5
+    return x, idx
 
 
 def _dgcnn_from_golden(g, dev, emb=64, k=10):

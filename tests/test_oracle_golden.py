@@ -11,6 +11,7 @@ import torch
 
 import oracle
 from oracle import reference as R
+from _shapes import KNN_CHANNELS
 from conftest import GOLDEN, rel_err, assert_knn_equivalent
 from dgx import synth
 
@@ -32,6 +33,20 @@ def test_oracle_knn_matches_reference(golden, case, layout):
     idx, vals = oracle.knn(x, k, return_values=True)
     np.testing.assert_array_equal(idx, g[key + "_idx"])
     np.testing.assert_array_equal(vals, g[key + "_val"])  # bit-exact distances
+
+
+@pytest.mark.parametrize("layout", ["bcn", "perm"])
+@pytest.mark.parametrize("C", KNN_CHANNELS)
+def test_oracle_knn_matches_reference_every_channel_tier(golden, C, layout):
+    """knn_channels.npz: one reference kNN per channel width, so the oracle's
+    restatement of torch's |x|^2 summation order (its C % 4 / % 8 / % 16 tails)
+    and of the sgemm chain is pinned in every kNN tier, not only at C in
+    {3, 9, 64, 128}."""
+    g = golden("knn_channels.npz")
+    key = f"c{C}_{layout}"
+    assert g[key + "_x"].shape[-1] == C
+    idx, vals = oracle.knn(_x_view(g[key + "_x"], layout), g[key + "_idx"].shape[-1], return_values=True)
+    assert_knn_equivalent(idx, vals, g[key + "_idx"], g[key + "_val"])   # values bit-exact
 
 
 def test_oracle_knn_ties(golden):

@@ -75,11 +75,19 @@ def _push(S, packed, bf16=False, fin=False, dz=None):
     return out, o
 
 
-def _pull(S, packed):
+def _pull(S, packed, mode=0):
+    """The pull scatter with out_bf16 = ``mode``: fp32 (M, 2Co), bf16 (M, 2Co), or
+    (modes 2 / 3) the bf16 planes (3, M, 2Co), zero where the mode writes none."""
     L, st = S["L"], S["st"]
-    out = torch.empty(S["M"], 2 * S["Co"], device=S["PQ"].device)
-    common = (S["B"], S["N"], S["k"], S["Co"], nat.f32(st.scale), nat.f32(S["c0"]), nat.f32(S["c1"]), nat.f32(out), 0,
-              S["stream"])
+    dev = S["PQ"].device
+    if mode == 0:
+        out = torch.empty(S["M"], 2 * S["Co"], device=dev)
+    elif mode == 1:
+        out = torch.empty(S["M"], 2 * S["Co"], device=dev, dtype=torch.bfloat16)
+    else:
+        out = torch.zeros(3, S["M"], 2 * S["Co"], device=dev, dtype=torch.bfloat16)
+    common = (S["B"], S["N"], S["k"], S["Co"], nat.f32(st.scale), nat.f32(S["c0"]), nat.f32(S["c1"]),
+              nat.ptr(out, nat.F32, nat.BF16), mode, S["stream"])
     if packed:
         nat.check(L.dgx_edge_bwd_scatter_packed_f32(nat.f32(S["PQ"]), 2 * S["Co"], nat.i32(S["rowptr"]),
                                                     nat.i32(S["edges"]), nat.f32(S["dz"]), nat.f32(S["sumP"]),
@@ -196,3 +204,107 @@ def test_pull_split_planes_output(cuda, packed, B, N, k, Co, mode):
     assert torch.equal(planes[2], hi if mode == 3 else torch.zeros_like(hi))
     with pytest.raises(RuntimeError):
         _push(S, packed, bf16=mode)
+
+
+# ---- the pull scatter's output modes at every slice geometry -------------------------------------------------------
+BW_LDS_BYTES = 72 * 1024   # csrc/edgeconv.hip: the Q | dz | slot slices of two workgroups per CU
+
+
+def _scatter_cs(N, packed):
+    """launch_scatter's slice width: 9 bytes per (point, channel) with slot bytes,
+    8 with packed dz|slot words, halved from 8 channels until the slice fits."""
+    cs = 8
+    while cs > 1 and (8 if packed else 9) * N * cs > BW_LDS_BYTES:
+        cs //= 2
+    return cs
+
+
+# one ragged N per geometry (the same for both dz forms): 8 / 4 / 2 / 1 channels
+# per slice within BW_LDS_BYTES, then one-channel slices beyond it (the 160 KiB mode)
+SCATTER_GEOMETRIES = [(1000, 8, False), (2003, 4, False), (4001, 2, False), (7001, 1, False), (12001, 1, True)]
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("N,cs,big", SCATTER_GEOMETRIES)
+def test_pull_output_modes_vs_fp64(cuda, N, cs, big, packed):
+    """Every out_bf16 mode of the pull scatter against the fp64 restatement:
+    fp32 within 2e-6 of the output scale; bf16 within its rounding, 2^-8 |ref|,
+    on top of that; the split planes hi + lo within 2^-15 |ref| on top of it
+    (lo = bf16(v - hi) leaves 2^-16 |v|); mode 3's third plane is the first."""
+    B, k, Co = 1, 8, 8
+    assert _scatter_cs(N, packed) == cs and ((8 if packed else 9) * N * cs > BW_LDS_BYTES) == big
+    S = _setup(cuda, B, N, k, Co, packed=packed, seed=9)
+    ref = _ref64(S, packed)
+    out = [_pull(S, packed, mode) for mode in range(4)]
+    torch.cuda.synchronize()
+    scale = float(ref.abs().max())
+    fp32_err = 2e-6 * scale
+    e0 = float((out[0].double() - ref).abs().max())
+    e1 = (out[1].double() - ref).abs() - 2.0 ** -8 * ref.abs()
+    print(f"N{N} cs{cs} packed={packed}: fp32 {e0 / scale:.2e}, bf16 excess {float(e1.max()) / scale:.2e}")
+    assert e0 < fp32_err
+    assert bool((e1 <= fp32_err).all())
+    for mode in (2, 3):
+        hi, lo, third = out[mode]
+        e = (hi.double() + lo.double() - ref).abs() - 2.0 ** -15 * ref.abs()
+        print(f"  mode {mode}: split excess {float(e.max()) / scale:.2e}")
+        assert bool((e <= fp32_err).all())
+        assert torch.equal(third, hi if mode == 3 else torch.zeros_like(hi))
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_pull_largest_cloud_and_one_more(cuda, packed):
+    """dgx_edge_bwd_scatter_max_n: the largest cloud runs and matches fp64; one
+    more point is refused by the entry's shape check, before any launch (the
+    output buffer is untouched)."""
+    B, k, Co = 1, 8, 8
+    L = nat.lib()
+    nmax = L.dgx_edge_bwd_scatter_max_n(B, Co, int(packed))
+    assert 17000 < nmax < 21000                       # about 17900 with slot bytes, 20000 packed
+    assert L.dgx_edge_bwd_scatter_fits(B, nmax, Co, int(packed)) == 1
+    assert L.dgx_edge_bwd_scatter_fits(B, nmax + 1, Co, int(packed)) == 0
+    S = _setup(cuda, B, nmax, k, Co, packed=packed, seed=13)
+    ref = _ref64(S, packed)
+    got = _pull(S, packed)
+    torch.cuda.synchronize()
+    assert _rel(got, ref) < 2e-6
+    S = _setup(cuda, B, nmax + 1, k, Co, packed=packed, seed=13)
+    out = torch.full((S["M"], 2 * Co), float("nan"), device=cuda)
+    st = S["st"]
+    common = (B, nmax + 1, k, Co, nat.f32(st.scale), nat.f32(S["c0"]), nat.f32(S["c1"]), nat.f32(out), 0, S["stream"])
+    if packed:
+        rc = L.dgx_edge_bwd_scatter_packed_f32(nat.f32(S["PQ"]), 2 * Co, nat.i32(S["rowptr"]), nat.i32(S["edges"]),
+                                               nat.f32(S["dz"]), nat.f32(S["sumP"]), *common)
+    else:
+        rc = L.dgx_edge_bwd_scatter_f32(nat.f32(S["PQ"]), 2 * Co, nat.i32(S["rowptr"]), nat.i32(S["edges"]),
+                                        nat.f32(S["dz"]), nat.u8(S["arg"]), nat.f32(S["sumP"]), *common)
+    torch.cuda.synchronize()
+    assert rc == -2 and L.dgx_strerror(rc) == b"unsupported shape"
+    assert bool(torch.isnan(out).all())
+
+
+@pytest.mark.parametrize("mode,packed", [("fp32", False), ("bf16", True)])
+def test_training_forward_names_the_backward_limit(cuda, mode, packed):
+    """A cloud the backward scatter cannot take is refused when the training
+    forward is entered, with the limit in the message; the same cloud runs
+    forward-only."""
+    from dgx import precision
+    from dgx.edgeconv import edgeconv_stack
+    B, C, Co, k = 1, 3, 8, 8
+    nmax = nat.lib().dgx_edge_bwd_scatter_max_n(B, Co, int(packed))
+    blk = torch.nn.Sequential(torch.nn.Conv2d(2 * C, Co, 1, bias=False), torch.nn.BatchNorm2d(Co),
+                              torch.nn.LeakyReLU(0.2)).to(cuda).train()
+    x = torch.randn(B, C, nmax + 1, generator=torch.Generator().manual_seed(1)).to(cuda)
+    precision.set(mode)
+    try:
+        with pytest.raises(RuntimeError, match=f"at most N = {nmax} points"):
+            edgeconv_stack(x.clone().requires_grad_(True), k, [blk], True)
+        with torch.no_grad():
+            y = edgeconv_stack(x, k, [blk], True)
+        ok = edgeconv_stack(x[:, :, :nmax].contiguous().requires_grad_(True), k, [blk], True)
+        ok.sum().backward()
+    finally:
+        precision.set("fp32")
+    torch.cuda.synchronize()
+    assert tuple(y.shape) == (B * (nmax + 1), Co) and bool(torch.isfinite(y).all())
+    assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in blk.parameters())
