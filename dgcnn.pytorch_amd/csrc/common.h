@@ -14,6 +14,19 @@
 
 static inline hipStream_t dgx_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// Split-K geometry of a SLAB launch with K-step bk: the k range of one slab (a
+// multiple of bk) and the slabs [slabs][M][N] the launch writes — fewer than
+// `splits` when K is short. The launchers' grids and the dgx_gemm*_slabs
+// queries (whoever allocates and sums the slabs) all come from here.
+struct DgxSplitK {
+    int kchunk, slabs;
+};
+static inline DgxSplitK dgx_split_k(int K, int splits, int bk) {
+    if (K <= 0 || splits < 1) return {bk, 1};
+    const int kchunk = ((K + splits - 1) / splits + bk - 1) / bk * bk;
+    return {kchunk, (K + kchunk - 1) / kchunk};
+}
+
 // XCD-aware block -> work-item map (MI355X_MICROARCH.md: blocks b and b+8 share
 // an XCD). Items are (cloud, tile) pairs; all tiles of one cloud get the same
 // block residue mod 8 so the cloud's rows are served from one XCD's L2:

@@ -23,6 +23,9 @@
 //   bn_batch_stats / bn_backward_consts   one layer's BatchNorm finalize, forward / backward (dgx.bn)
 //   dgcnn                                 DGCNN.forward as one op with a C++ autograd node
 //                                         (eager training: ~60 launches without a Python frame)
+//   gemm_xwt / gemm_xw / gemm_atb / gemm32 / gemm_edge_dz_ok / weight_prep / weight_prep_one
+//                                         the schedule's GEMM and weight-prep helpers, one op each (dgx.gemm)
+//   weight_prep_layout                    the weight-prep buffer's layout, host only (dgx.gemm.prep_layout restates it)
 //   knn_timing                            per-thread HIP-event timing of the kNN selection launches
 //   layout                                the name tables of the saved-state lists and the opts word
 //                                         (dgx.schedule names the same fields: one layout, checked by a test)
@@ -328,6 +331,8 @@ struct SlabJobs {
 };
 
 void reduce_slab(const Dev& d, const Tensor& slab, int used, int M, int N, int split, Tensor& out, SlabJobs* defer) {
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && (out.stride(1) == 1 || out.size(1) == 1),
+              "dgx gemm: output must be a row-major fp32 view");
   if (defer) {
     defer->add(d, slab, used, M, N, split, out);
     return;
@@ -335,14 +340,14 @@ void reduce_slab(const Dev& d, const Tensor& slab, int used, int M, int N, int s
   check(dgx_slab_reduce_f32(P(slab), used, M, N, split, P(out), out.stride(0), d.stream), "slab reduce");
 }
 
-// dgx.gemm._operand: row stride of a 2-D row-major operand
+// row stride of a 2-D row-major fp32 / bf16 operand
 int64_t ld2(const Tensor& t) {
   TORCH_CHECK(t.dim() == 2 && (t.stride(1) == 1 || t.size(1) == 1),
               "dgx gemm: operand must be a 2-D row-major view, got strides ", t.strides());
   TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16, "dgx gemm: fp32/bf16 operands only");
   return t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(1, t.size(1));
 }
-// dgx.gemm._bf16_2d
+// row stride of a bf16 operand of the LDS-DMA path
 int64_t ld16(const Tensor& t) {
   TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 2 && (t.stride(1) == 1 || t.size(1) == 1),
               "dgx gemm (bf16 path): operands must be row-major bf16 2-D views");
@@ -350,7 +355,7 @@ int64_t ld16(const Tensor& t) {
 }
 bool is16(const Tensor& t) { return t.scalar_type() == at::kBFloat16; }
 
-// dgx.gemm.gemm: register-staged bf16 MFMA GEMM, fp32 or bf16 operands
+// register-staged bf16 MFMA GEMM, fp32 or bf16 operands
 void gemm16(const Dev& d, const Tensor& a, bool a_ic, const Tensor& b, bool b_ic, int M, int N, int K, int epi,
             float* out, int64_t ldc, float* part, int splits) {
   check(dgx_gemm_bf16(a.data_ptr(), is16(a), a_ic, ld2(a), b.data_ptr(), is16(b), b_ic, ld2(b), M, N, K, epi, splits,
@@ -359,9 +364,11 @@ void gemm16(const Dev& d, const Tensor& a, bool a_ic, const Tensor& b, bool b_ic
 }
 
 // out (M,N) = x (M,K) w (N,K)^T (+ BN column partials)
-Tensor mm_xwt(const Dev& d, const Tensor& x, const Tensor& w, Tensor* part) {
+Tensor mm_xwt(const Dev& d, const Tensor& x, const Tensor& w, Tensor* part, Tensor* out_view = nullptr) {
   const int M = (int)x.size(0), K = (int)x.size(1), N = (int)w.size(0);
-  Tensor out = at::empty({M, N}, d.f32);
+  Tensor out = out_view ? *out_view : at::empty({M, N}, d.f32);
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && (out.stride(1) == 1 || N == 1),
+              "dgx gemm: output must be a row-major fp32 view");
   if (part) *part = at::empty({dgx_gemm_stats_rows(M), 2, N}, d.f32);
   gemm16(d, x, false, w, false, M, N, K, part ? kEpiStats : kEpiStore, P(out), out.stride(0), part ? P(*part) : nullptr,
          1);
@@ -382,10 +389,7 @@ void mm_atb(const Dev& d, const Tensor& a, const Tensor& b, Tensor& out, int spl
   const int S = dgx_gemm_splits(M, N, R);
   Tensor slab = at::empty({S, M, N}, d.f32);
   gemm16(d, a, true, b, true, M, N, R, kEpiSlab, P(slab), N, nullptr, S);
-  int64_t chunk = cdiv(R, S);
-  chunk = cdiv(chunk, 32) * 32;
-  const int used = (int)cdiv(R, chunk);
-  reduce_slab(d, slab, used, M, N, split_rows > 0 ? split_rows : M, out, defer);
+  reduce_slab(d, slab, dgx_gemm_slabs(R, S), M, N, split_rows > 0 ? split_rows : M, out, defer);
 }
 
 // out (M,N) = a (M,K) b (K,N), fp32 or bf16 operands rounded to bf16 while staged; transposed
@@ -410,7 +414,7 @@ bool lds_ok(const Tensor& x16, int64_t K) {
          reinterpret_cast<uintptr_t>(x16.data_ptr()) % 16 == 0;
 }
 
-// dgx.gemm.lds_xwt: out (M,N) = x16 (M,K) w16 (N,Kw)^T (Kw = 2K: split weight [hi | lo]);
+// out (M,N) = x16 (M,K) w16 (N,Kw)^T (Kw = 2K: split weight [hi | lo]);
 // part: BN column partials (with out_bf16 the product is stored bf16); addend: out = addend + ...
 Tensor lds_xwt(const Dev& d, const Tensor& x16, const Tensor& w16, Tensor* part, bool out_bf16,
                const Tensor* addend = nullptr, Tensor* out_view = nullptr) {
@@ -418,6 +422,10 @@ Tensor lds_xwt(const Dev& d, const Tensor& x16, const Tensor& w16, Tensor* part,
   TORCH_CHECK(Kw == K || Kw == 2 * K, "dgx gemm: weight k extent does not match the operand's");
   TORCH_CHECK(!out_bf16 || part, "dgx gemm: a bf16 product is only stored together with its statistics");
   Tensor out = out_view ? *out_view : at::empty({M, N}, out_bf16 ? d.bf16 : d.f32);
+  TORCH_CHECK(out.scalar_type() == (out_bf16 ? at::kBFloat16 : at::kFloat) && out.dim() == 2 && out.stride(1) == 1,
+              "dgx gemm: output view dtype/layout does not match the epilogue");
+  TORCH_CHECK(!addend || (addend->scalar_type() == at::kFloat && addend->dim() == 2 && addend->stride(1) == 1),
+              "dgx gemm: addend must be a row-major fp32 view");
   if (part) *part = at::empty({dgx_gemm_stats_rows(M), 2, N}, d.f32);
   const int epi = part ? (out_bf16 ? kEpiStats16 : kEpiStats) : (addend ? kEpiAccum : kEpiStore);
   check(dgx_gemm_lds_bf16(x16.data_ptr(), ld16(x16), w16.data_ptr(), ld16(w16), 0, M, N, Kw, K, epi, 1, P(out),
@@ -427,16 +435,14 @@ Tensor lds_xwt(const Dev& d, const Tensor& x16, const Tensor& w16, Tensor* part,
   return out;
 }
 
-// dgx.gemm.lds_atb: out = a16^T b16 (split-K slabs, the small-output slab cap)
+// out = a16^T b16 (split-K slabs, the small-output slab cap)
 void lds_atb(const Dev& d, const Tensor& a16, const Tensor& b16, Tensor& out, int split_rows, int64_t slab_cap_mb,
              SlabJobs* defer) {
   const int R = (int)a16.size(0), M = (int)a16.size(1), N = (int)b16.size(1);
   int S = dgx_gemm_splits(M, N, R);
   const int64_t bytes = (int64_t)M * N * 4;
   if (slab_cap_mb > 0 && bytes < (1 << 20)) S = (int)std::max<int64_t>(1, std::min<int64_t>(S, (slab_cap_mb << 20) / bytes));
-  int64_t chunk = cdiv(R, S);
-  chunk = cdiv(chunk, 64) * 64;
-  const int used = (int)cdiv(R, chunk);
+  const int used = dgx_gemm_lds_slabs(R, S);
   Tensor slab = at::empty({used, M, N}, d.f32);
   check(dgx_gemm_lds_bf16(a16.data_ptr(), ld16(a16), b16.data_ptr(), ld16(b16), 1, M, N, R, R, kEpiSlab, S, P(slab), N,
                           nullptr, nullptr, 0, d.stream),
@@ -449,9 +455,7 @@ void lds_atb(const Dev& d, const Tensor& a16, const Tensor& b16, Tensor& out, in
 void lds_atb_sum(const Dev& d, const std::vector<std::pair<Tensor, Tensor>>& ab, Tensor& out, SlabJobs* defer) {
   const int R = (int)ab[0].first.size(0), M = (int)ab[0].first.size(1), N = (int)ab[0].second.size(1);
   const int S = dgx_gemm_splits(M, N, R);
-  int64_t chunk = cdiv(R, S);
-  chunk = cdiv(chunk, 64) * 64;
-  const int used = (int)cdiv(R, chunk);
+  const int used = dgx_gemm_lds_slabs(R, S);
   const int n = (int)ab.size();
   Tensor slab = at::empty({(int64_t)n * used, M, N}, d.f32);
   for (int i = 0; i < n; ++i) {
@@ -472,14 +476,14 @@ std::pair<Tensor, Tensor> split16(const Dev& d, const Tensor& x) {
   return {hi, lo};
 }
 
-// dgx.gemm.edge_dz_ok
+// whether dgx_gemm_edge_dz_bf16 takes this block's input-gradient GEMM (dX columns = cin, K = dPQ width)
 bool edge_dz_ok(const Tensor& dpq16, int cin) {
   const int64_t K = dpq16.size(1);
   return is16(dpq16) && cin % 8 == 0 && cin <= 128 && K % 64 == 0 && dpq16.stride(0) % 8 == 0 &&
          reinterpret_cast<uintptr_t>(dpq16.data_ptr()) % 16 == 0;
 }
 
-// dgx.gemm._op32: (tensor, ic, ld) of an fp32 operand read in place; kd = the dim holding "k"
+// (tensor, ic, ld) of an fp32 operand read in place; kd = the dim holding "k"
 struct Op32 {
   Tensor t;
   int ic;
@@ -496,28 +500,30 @@ Op32 op32(Tensor t, int kd) {
   return op32(t, kd);
 }
 
-// dgx.gemm.mm32: out (M,N) (+)= a (M,K) b (K,N) on the fp32 MFMA GEMM (parity mode);
+// out (M,N) (+)= a (M,K) b (K,N) on the fp32 MFMA GEMM (parity mode); addend: out = addend + a b;
 // a long reduction over few outputs (the weight gradients) is split-K, summed in a fixed order
-Tensor mm32(const Dev& d, const Tensor& a, const Tensor& b, Tensor* out_view, bool accumulate) {
+Tensor mm32(const Dev& d, const Tensor& a, const Tensor& b, Tensor* out_view, bool accumulate,
+            const Tensor* addend = nullptr) {
   const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(1);
   TORCH_CHECK(b.size(0) == K, "dgx mm32: inner dims differ");
   Op32 A = op32(a, 1), Bo = op32(b, 0);
   Tensor out = out_view ? *out_view : at::empty({M, N}, d.f32);
   TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && (out.stride(1) == 1 || N == 1),
               "dgx mm32: output must be a row-major fp32 2-D view");
-  const int S = (K >= 2048 && !accumulate) ? dgx_gemm_f32_splits(M, N, K) : 1;
+  TORCH_CHECK(!addend || (addend->scalar_type() == at::kFloat && addend->dim() == 2 && addend->stride(1) == 1),
+              "dgx mm32: addend must be a row-major fp32 view");
+  const int S = (K >= 2048 && !accumulate && !addend) ? dgx_gemm_f32_splits(M, N, K) : 1;
   if (S > 1) {
-    int64_t kchunk = cdiv(K, S);
-    kchunk = cdiv(kchunk, 16) * 16;
-    const int used = (int)cdiv(K, kchunk);
+    const int used = dgx_gemm_f32_slabs(K, S);
     Tensor slab = at::empty({used, M, N}, d.f32);
     check(dgx_gemm_f32(P(A.t), A.ic, (int)A.ld, P(Bo.t), Bo.ic, (int)Bo.ld, M, N, K, kEpiSlab, S, P(slab), N, nullptr, 0,
                        d.stream),
           "gemm f32 (split-K)");
     check(dgx_slab_reduce_f32(P(slab), used, M, N, M, P(out), out.stride(0), d.stream), "slab reduce");
   } else {
-    check(dgx_gemm_f32(P(A.t), A.ic, (int)A.ld, P(Bo.t), Bo.ic, (int)Bo.ld, M, N, K, accumulate ? kEpiAccum : kEpiStore,
-                       1, P(out), M > 1 ? out.stride(0) : std::max(N, 1), nullptr, 0, d.stream),
+    check(dgx_gemm_f32(P(A.t), A.ic, (int)A.ld, P(Bo.t), Bo.ic, (int)Bo.ld, M, N, K,
+                       (accumulate || addend) ? kEpiAccum : kEpiStore, 1, P(out), M > 1 ? out.stride(0) : std::max(N, 1),
+                       addend ? P(*addend) : nullptr, addend ? addend->stride(0) : 0, d.stream),
           "gemm f32");
   }
   return out;
@@ -532,9 +538,7 @@ void mm32_atb(const Dev& d, const Tensor& a, const Tensor& b, Tensor& out, int s
   TORCH_CHECK(b.size(0) == R, "dgx mm32_atb: row counts differ");
   Op32 A = op32(a.t(), 1), Bo = op32(b, 0);
   const int S = dgx_gemm_f32_splits(M, N, R);
-  int64_t kchunk = cdiv(R, S);
-  kchunk = cdiv(kchunk, 16) * 16;
-  const int used = (int)cdiv(R, kchunk);
+  const int used = dgx_gemm_f32_slabs(R, S);
   Tensor slab = at::empty({used, M, N}, d.f32);
   check(dgx_gemm_f32(P(A.t), A.ic, (int)A.ld, P(Bo.t), Bo.ic, (int)Bo.ld, M, N, R, kEpiSlab, S, P(slab), N, nullptr, 0,
                      d.stream),
@@ -549,7 +553,8 @@ Tensor split_weight(const Tensor& w, int cin, int co) {
 }
 
 // -------------------------------------------------------- bf16 weight prep ----
-// dgx.gemm.prep_layout: one bf16 buffer, per job (nt (R, [2]C), tn (C, R)), 16-byte aligned views
+// one bf16 buffer, per job (nt (R, [2]C), tn (C, R)), 16-byte aligned views (dgx.gemm.prep_layout restates
+// this layout for the tracing paths; dgx_host::weight_prep_layout reports it and a test holds the two equal)
 struct PrepJob {
   Tensor w;
   int rows, cols;
@@ -573,20 +578,25 @@ std::vector<std::pair<Tensor, Tensor>> prep_views(const Tensor& buf, const std::
   return v;
 }
 
-// one plain weight's bf16 copies: (nt (rows, cols), tn (cols, rows))
-std::pair<Tensor, Tensor> prep_weight(const Dev& d, const Tensor& w, int rows, int cols) {
-  Tensor nt = at::empty({rows, cols}, d.bf16), tn = at::empty({cols, rows}, d.bf16);
+// one weight's bf16 copies: (nt (R, cols), tn (cols, R)), R = 2 rows for a stacked EdgeConv weight [W1; W2]
+std::pair<Tensor, Tensor> prep_weight(const Dev& d, const Tensor& w, int rows, int cols, bool stacked = false) {
+  TORCH_CHECK(w.scalar_type() == at::kFloat, "dgx weight prep: fp32 weights expected");
+  const int R = stacked ? 2 * rows : rows;
+  Tensor nt = at::empty({R, cols}, d.bf16), tn = at::empty({cols, R}, d.bf16);
   Tensor wc = w.contiguous();
-  check(dgx_weight_prep_bf16(P(wc), rows, cols, 0, nt.data_ptr(), tn.data_ptr(), d.stream), "weight prep");
+  check(dgx_weight_prep_bf16(P(wc), rows, cols, stacked, nt.data_ptr(), tn.data_ptr(), d.stream), "weight prep");
   return {nt, tn};
 }
 
-// every job's bf16 copies in one launch
-std::pair<Tensor, std::vector<std::pair<Tensor, Tensor>>> prep_weights(const Dev& d, const std::vector<PrepJob>& jobs) {
+// every job's bf16 copies in one launch, into `buf` when given
+std::pair<Tensor, std::vector<std::pair<Tensor, Tensor>>> prep_weights(const Dev& d, const std::vector<PrepJob>& jobs,
+                                                                       Tensor buf = Tensor()) {
   TORCH_CHECK(jobs.size() <= 8, "dgx weight prep: at most 8 weights per launch");
   int64_t total = 0;
   prep_views(Tensor(), jobs, &total);
-  Tensor buf = at::empty({total}, d.bf16);
+  if (!buf.defined()) buf = at::empty({total}, d.bf16);
+  TORCH_CHECK(buf.numel() == total && buf.scalar_type() == at::kBFloat16 && buf.is_contiguous(),
+              "dgx weight prep: buffer does not match the jobs' layout");
   auto views = prep_views(buf, jobs);
   const int n = (int)jobs.size();
   std::vector<Tensor> keep(n);
@@ -1729,6 +1739,97 @@ std::vector<Tensor> bn_backward_consts(const Tensor& partials, int64_t rows, dou
   return {r[0], r[1], r[2], r[3]};
 }
 
+// ---- the GEMM helpers above as ops (dgx.gemm binds them: tests and tools drive the schedule's own GEMMs) ----
+Tensor out_or_none(const std::optional<Tensor>& t) { return t.has_value() ? *t : Tensor(); }
+
+// dgx_host::gemm_xwt -> (out, BN column partials or empty): lds ? lds_xwt : mm_xwt
+std::tuple<Tensor, Tensor> gemm_xwt(const Tensor& x, const Tensor& w, std::optional<Tensor> out, bool stats,
+                                    bool out_bf16, const std::optional<Tensor>& addend, bool lds) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Dev d(x);
+  Tensor o = out_or_none(out), add = out_or_none(addend), part;
+  Tensor r = lds ? lds_xwt(d, x, w, stats ? &part : nullptr, out_bf16, add.defined() ? &add : nullptr,
+                           o.defined() ? &o : nullptr)
+                 : mm_xwt(d, x, w, stats ? &part : nullptr, o.defined() ? &o : nullptr);
+  return {r, stats ? part : at::empty({0}, d.f32)};
+}
+
+// dgx_host::gemm_xw -> out (+)= x w (mm_xw)
+Tensor gemm_xw(const Tensor& x, const Tensor& w, std::optional<Tensor> out, bool accumulate) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Dev d(x);
+  TORCH_CHECK(out.has_value() || !accumulate, "dgx gemm: accumulate needs an output to accumulate into");
+  Tensor o = out.has_value() ? *out : at::empty({x.size(0), w.size(1)}, d.f32);
+  mm_xw(d, x, w, o, accumulate);
+  return o;
+}
+
+// dgx_host::gemm_atb: out = a^T b, lds ? lds_atb (with the slab cap) : mm_atb
+void gemm_atb(const Tensor& a, const Tensor& b, Tensor out, int64_t split_rows, bool lds, int64_t slab_cap_mb) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+  Dev d(a);
+  if (lds) lds_atb(d, a, b, out, (int)split_rows, slab_cap_mb, nullptr);
+  else mm_atb(d, a, b, out, (int)split_rows, nullptr);
+}
+
+// dgx_host::gemm32 -> out (mm32)
+Tensor gemm32(const Tensor& a, const Tensor& b, std::optional<Tensor> out, bool accumulate,
+              const std::optional<Tensor>& addend) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+  Dev d(a);
+  TORCH_CHECK(out.has_value() || !accumulate, "dgx mm32: accumulate=True needs an output to accumulate into");
+  Tensor o = out_or_none(out), add = out_or_none(addend);
+  return mm32(d, a, b, o.defined() ? &o : nullptr, accumulate, add.defined() ? &add : nullptr);
+}
+
+bool gemm_edge_dz_ok(const Tensor& dpq16, int64_t cin) { return edge_dz_ok(dpq16, (int)cin); }
+
+std::vector<PrepJob> prep_jobs(at::TensorList weights, const std::vector<int64_t>& rows, const std::vector<int64_t>& cols,
+                               const c10::List<bool>& stacked, const c10::List<bool>& split) {
+  const size_t n = rows.size();
+  TORCH_CHECK(cols.size() == n && stacked.size() == n && split.size() == n && (weights.empty() || weights.size() == n),
+              "dgx weight prep: per-job lists differ in length");
+  std::vector<PrepJob> jobs(n);
+  for (size_t j = 0; j < n; ++j)
+    jobs[j] = PrepJob{weights.empty() ? Tensor() : weights[j], (int)rows[j], (int)cols[j], stacked.get(j), split.get(j)};
+  return jobs;
+}
+
+// dgx_host::weight_prep -> the shared bf16 buffer of prep_weights (filled in place when given)
+Tensor weight_prep(at::TensorList weights, std::vector<int64_t> rows, std::vector<int64_t> cols,
+                   const c10::List<bool>& stacked, const c10::List<bool>& split, std::optional<Tensor> buf) {
+  TORCH_CHECK(!weights.empty(), "dgx weight prep: no weights");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(weights[0].device());
+  Dev d(weights[0]);
+  return prep_weights(d, prep_jobs(weights, rows, cols, stacked, split), out_or_none(buf)).first;
+}
+
+// dgx_host::weight_prep_one -> (nt, tn) of one weight by the single-weight kernel (prep_weight)
+std::tuple<Tensor, Tensor> weight_prep_one(const Tensor& w, int64_t rows, int64_t cols, bool stacked) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(w.device());
+  Dev d(w);
+  auto r = prep_weight(d, w, (int)rows, (int)cols, stacked);
+  return {r.first, r.second};
+}
+
+// dgx_host::weight_prep_layout (host only) -> total elements, then per job the offset and (rows, cols) of the nt
+// and tn views prep_views cuts — read off views of a meta buffer, so these are the schedule's own views
+std::tuple<int64_t, std::vector<int64_t>, std::vector<int64_t>, std::vector<int64_t>, std::vector<int64_t>>
+weight_prep_layout(std::vector<int64_t> rows, std::vector<int64_t> cols, const c10::List<bool>& stacked,
+                   const c10::List<bool>& split) {
+  auto jobs = prep_jobs(at::TensorList(), rows, cols, stacked, split);
+  int64_t total = 0;
+  prep_views(Tensor(), jobs, &total);
+  std::vector<int64_t> nt_off, nt_shape, tn_off, tn_shape;
+  for (const auto& v : prep_views(at::empty({total}, at::device(at::kMeta).dtype(at::kBFloat16)), jobs)) {
+    nt_off.push_back(v.first.storage_offset());
+    nt_shape.insert(nt_shape.end(), v.first.sizes().begin(), v.first.sizes().end());
+    tn_off.push_back(v.second.storage_offset());
+    tn_shape.insert(tn_shape.end(), v.second.sizes().begin(), v.second.sizes().end());
+  }
+  return {total, nt_off, nt_shape, tn_off, tn_shape};
+}
+
 // DGCNN.forward (dgcnn.py:80-103) as one op: the EdgeConv chain + conv5 forward and,
 // from a C++ autograd node, the whole backward. Every mode (bf16 / fp32, train / eval,
 // SyncBatchNorm) runs the chain_* / pointconv_* schedule above.
@@ -1971,6 +2072,17 @@ TORCH_LIBRARY(dgx_host, m) {
         "float[] bn_f, int[] bn_i, str group) -> Tensor[]");
   m.def("bn_backward_consts(Tensor partials, int rows, float count, Tensor scale, Tensor mean, Tensor invstd, "
         "bool eval, str group) -> Tensor[]");
+  m.def("gemm_xwt(Tensor x, Tensor w, Tensor(a!)? out, bool stats, bool out_bf16, Tensor? addend, bool lds) "
+        "-> (Tensor(a), Tensor)");
+  m.def("gemm_xw(Tensor x, Tensor w, Tensor(a!)? out, bool accumulate) -> Tensor(a)");
+  m.def("gemm_atb(Tensor a, Tensor b, Tensor(c!) out, int split_rows, bool lds, int slab_cap_mb) -> ()");
+  m.def("gemm32(Tensor a, Tensor b, Tensor(c!)? out, bool accumulate, Tensor? addend) -> Tensor(c)");
+  m.def("gemm_edge_dz_ok(Tensor dpq16, int cin) -> bool");
+  m.def("weight_prep(Tensor[] weights, int[] rows, int[] cols, bool[] stacked, bool[] split, Tensor(a!)? buf) "
+        "-> Tensor(a)");
+  m.def("weight_prep_one(Tensor w, int rows, int cols, bool stacked) -> (Tensor, Tensor)");
+  m.def("weight_prep_layout(int[] rows, int[] cols, bool[] stacked, bool[] split) -> (int total, int[] nt_offset, "
+        "int[] nt_shape, int[] tn_offset, int[] tn_shape)", &weight_prep_layout);
   m.def("layout() -> (str[] chain_fields, str[] pointconv_fields, str[] opts_bits, str[] edge_mlp_fields)", &layout);
 }
 
@@ -1987,4 +2099,11 @@ TORCH_LIBRARY_IMPL(dgx_host, CompositeExplicitAutograd, m) {
   m.impl("edge_mlp2_backward", edge_mlp2_backward);
   m.impl("bn_batch_stats", bn_batch_stats);
   m.impl("bn_backward_consts", bn_backward_consts);
+  m.impl("gemm_xwt", gemm_xwt);
+  m.impl("gemm_xw", gemm_xw);
+  m.impl("gemm_atb", gemm_atb);
+  m.impl("gemm32", gemm32);
+  m.impl("gemm_edge_dz_ok", gemm_edge_dz_ok);
+  m.impl("weight_prep", weight_prep);
+  m.impl("weight_prep_one", weight_prep_one);
 }

@@ -1136,9 +1136,7 @@ int launch_gemm256(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, int M
 template <bool TN, int BN, int EPI>
 int launch_gemm_lds(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, int M, int N, int K, int ka, int splits,
                     float* C, int64_t ldc, float* part, const float* addend, int64_t ldd, hipStream_t st) {
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = (kchunk + G2_BK - 1) / G2_BK * G2_BK;
-    const int sp = (K + kchunk - 1) / kchunk;
+    const auto [kchunk, sp] = dgx_split_k(K, splits, G2_BK);
     const int nJ = (N + BN - 1) / BN;
     // skinny outputs (few 128-row tiles): 64-row tiles double the workgroups so
     // two share each CU and hide each other's load latency
@@ -1291,9 +1289,7 @@ template <typename TA, bool AIC, typename TB, bool BIC, int BN, int EPI>
 int launch_gemm(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K, int splits,
                 int vec_a, int vec_b, float* C, int64_t ldc, float* part, hipStream_t st) {
     const int nI = (M + GB_BM - 1) / GB_BM, nJ = (N + BN - 1) / BN;
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = (kchunk + GB_BK - 1) / GB_BK * GB_BK;
-    const int sp = (K + kchunk - 1) / kchunk;
+    const auto [kchunk, sp] = dgx_split_k(K, splits, GB_BK);
     dim3 grid((unsigned)(nI * nJ), (unsigned)(EPI == EPI_SLAB ? sp : 1));
     hipLaunchKernelGGL((gemm_bf16_kernel<TA, AIC, TB, BIC, BN, EPI>), grid, dim3(GB_THREADS), 0, st,
                        static_cast<const TA*>(A), lda, static_cast<const TB*>(B), ldb, M, N, K,
@@ -1436,6 +1432,9 @@ int dgx_gemm_splits(int M, int N, int K) {
     return s < 1 ? 1 : s;
 }
 
+int dgx_gemm_slabs(int K, int splits) { return dgx_split_k(K, splits, GB_BK).slabs; }
+int dgx_gemm_lds_slabs(int K, int splits) { return dgx_split_k(K, splits, G2_BK).slabs; }
+
 int dgx_gemm_bf16(const void* A, int a_bf16, int a_ic, int64_t lda, const void* B, int b_bf16, int b_ic,
                   int64_t ldb, int M, int N, int K, int epi, int splits, float* C, int64_t ldc, float* partials,
                   void* stream) {
@@ -1467,9 +1466,7 @@ int dgx_gemm_bf16(const void* A, int a_bf16, int a_ic, int64_t lda, const void* 
     }
     if (a_ic && b_ic && !b_bf16 && epi == EPI_SLAB) {  // dPQ^T X / dZ^T X: weight gradients
         if (a_bf16 && N <= 4) {  // same split geometry (kchunk, slab count) as launch_gemm
-            int kchunk = (K + splits - 1) / splits;
-            kchunk = (kchunk + GB_BK - 1) / GB_BK * GB_BK;
-            const int sp = (K + kchunk - 1) / kchunk;
+            const auto [kchunk, sp] = dgx_split_k(K, splits, GB_BK);
             hipLaunchKernelGGL(atb_small_kernel<4>, dim3((unsigned)sp), dim3(256), 0, st, static_cast<const bf16*>(A),
                                lda, static_cast<const float*>(B), ldb, M, N, K, kchunk, C);
             return hipGetLastError() == hipSuccess ? DGX_OK : DGX_ELAUNCH;

@@ -158,9 +158,7 @@ int dgx_gemm_f32(const float* A, int a_ic, int lda, const float* B, int b_ic, in
     if (M == 0 || N == 0) return DGX_OK;
     if (epi != E32_SLAB && ldc < N) return DGX_EINVAL;
     const int ntm = (M + G32_BM - 1) / G32_BM, ntn = (N + G32_BN - 1) / G32_BN;
-    int kchunk = (K + splits - 1) / splits;
-    kchunk = ((kchunk + G32_BK - 1) / G32_BK) * G32_BK;
-    const int used = K > 0 ? (K + kchunk - 1) / kchunk : 1;
+    const auto [kchunk, used] = dgx_split_k(K, splits, G32_BK);
     if (epi != E32_SLAB && used > 1) return DGX_EINVAL;   // split-K only through slabs
     const bool avec = lda % 4 == 0 && al16f(A), bvec = ldb % 4 == 0 && al16f(B);
     const dim3 grid((unsigned)(ntm * ntn), (unsigned)used);
@@ -191,5 +189,7 @@ int dgx_gemm_f32_splits(int M, int N, int K) {
     s = s < cap ? s : cap;
     return s < 1 ? 1 : (s > 256 ? 256 : s);
 }
+
+int dgx_gemm_f32_slabs(int K, int splits) { return dgx_split_k(K, splits, G32_BK).slabs; }
 
 }  // extern "C"

@@ -234,12 +234,9 @@ torch.library.register_autocast("dgx::graph_feature", "cuda", torch.float32)
 def weight_prep(weights: list[Tensor], rows: list[int], cols: list[int], stacked: list[bool],
                 split: list[bool]) -> Tensor:
     """One bf16 buffer holding every weight's GEMM operand copies
-    (gemm.prep_layout: [W | W_hi W_lo] and W^T per weight), one launch."""
-    shapes = list(zip(rows, cols, stacked, split))
-    total, _ = G.prep_layout(shapes)
-    buf = torch.empty(total, dtype=_BF16, device=weights[0].device)
-    G.prep_weights([(w.detach(), r, c, st, sp) for w, (r, c, st, sp) in zip(weights, shapes)], buf=buf)
-    return buf
+    (gemm.prep_layout: [W | W_hi W_lo] and W^T per weight), one launch:
+    the C++ schedule's own allocation and views (dgx_host::weight_prep)."""
+    return S.host_ops().weight_prep([w.detach() for w in weights], rows, cols, stacked, split, None)
 
 
 @weight_prep.register_fake

@@ -2,7 +2,8 @@
 csrc/dgx_torch.cpp): every ``torch.ops.dgx_host`` call of the EdgeConv chain,
 conv5, PositionEmbedding's edge MLP and the one-op DGCNN goes through here, for
 the eager op (dgx.host), the autograd Functions (dgx.edgeconv, dgx.pointconv,
-dgx.edgemlp) and the torch.library ops (dgx.library) alike. What they share lives here once: the precision / options
+dgx.edgemlp) and the torch.library ops (dgx.library) alike; dgx.gemm binds the
+schedule's GEMM and weight-prep helpers through ``host_ops``. What they share lives here once: the precision / options
 decision taken at forward entry, the BatchNorm argument lists, the kNN-sharing
 lookup, and the names of the saved-state lists the schedule hands back for
 backward (``dgx_host::layout()`` returns the C++ side's tables; a test holds
@@ -105,6 +106,10 @@ def _host():
     from . import host
     host.load()
     return torch.ops.dgx_host
+
+
+# dgx.gemm's handle: its functions are the dgx_host::gemm_* / weight_prep* ops one to one, with nothing to share here
+host_ops = _host
 
 
 def chain_forward(x, k, weights, gammas, betas, bn, d, need_grad, prep, idx0):

@@ -379,6 +379,15 @@ int dgx_pointconv_bwd_split_f32(const float* dout, const float* Z, int B, int N,
  * epi 0/1; (fp32|bf16 IC, fp32 IC) epi 3. Others: DGX_EUNSUPPORTED. */
 int dgx_gemm_stats_rows(int M);
 int dgx_gemm_splits(int M, int N, int K);
+/* Slabs [used][M][N] a split-K (epi 3) launch with this (K, splits) writes:
+ * ceil(K / kchunk), kchunk = ceil(K / splits) rounded up to the kernel's
+ * K-step — fewer than `splits` when K is short; 1 for K <= 0 or splits < 1.
+ * Host arithmetic only. One per launcher: dgx_gemm_bf16, dgx_gemm_lds_bf16
+ * (tn = 1), dgx_gemm_f32. Whoever allocates the slab workspace and calls
+ * dgx_slab_reduce_f32 takes its S from here. */
+int dgx_gemm_slabs(int K, int splits);
+int dgx_gemm_lds_slabs(int K, int splits);
+int dgx_gemm_f32_slabs(int K, int splits);
 int dgx_gemm_bf16(const void* A, int a_bf16, int a_ic, int64_t lda,
                   const void* B, int b_bf16, int b_ic, int64_t ldb,
                   int M, int N, int K, int epi, int splits,

@@ -221,6 +221,33 @@ def test_weight_prep_split(cuda):
         assert torch.equal(tn, hi.t().contiguous())
 
 
+def test_weight_prep_op_buffer(cuda):
+    """dgx::weight_prep (the op torch.compile / export trace) fills the C++
+    schedule's buffer; read through prep_views (the Python restatement of its
+    layout) every job equals prep_weights of that job alone bit for bit, the
+    plain job also the single-weight kernel, and the alignment padding the
+    5 x 3 job forces lies outside every view."""
+    from dgx import gemm as G, library  # noqa: F401  (registers torch.ops.dgx)
+    torch.manual_seed(8)
+    shapes = [(8, 8, True, True), (16, 8, True, True), (5, 3, True, True), (40, 24, False, False)]
+    ws = [torch.randn(r, 2 * c if st else c, 1, 1, device=cuda) for (r, c, st, _) in shapes]
+    buf = torch.ops.dgx.weight_prep(ws, *(list(f) for f in zip(*shapes)))
+    total, lay = G.prep_layout(shapes)
+    assert buf.dtype == torch.bfloat16 and buf.shape == (total,)
+    covered = torch.zeros(total, dtype=torch.bool)
+    for w, sh, (nt, tn), (o1, s1, o2, s2) in zip(ws, shapes, G.prep_views(buf, shapes), lay):
+        (ent, etn), = G.prep_weights([(w,) + sh])
+        assert torch.equal(nt, ent) and torch.equal(tn, etn), sh
+        if not (sh[2] or sh[3]):
+            pnt, ptn = G.prep_weight(w, sh[0], sh[1], False)
+            assert torch.equal(nt, pnt) and torch.equal(tn, ptn)
+        for o, s in ((o1, s1), (o2, s2)):
+            assert o % 8 == 0 and not covered[o:o + s[0] * s[1]].any()
+            covered[o:o + s[0] * s[1]] = True
+    # 5 x 3 stacked + split: nt 60 -> 64, tn 30 -> 32 elements: 6 padding elements no view reads
+    assert int((~covered).sum()) == 6
+
+
 @pytest.mark.parametrize("M,N,K", [(4096, 128, 64), (3000, 512, 128), (32768, 1024, 512)])
 def test_lds_xwt_split_weight(cuda, M, N, K):
     """x16 [W_hi | W_lo]^T with the A tile reused for both halves equals the fp64

@@ -88,6 +88,13 @@ def test_host_op_library_loads():
         "edge_mlp2_forward": "dgx_host::edge_mlp2_forward(Tensor x, Tensor idx, int k, Tensor w1",
         "edge_mlp2_backward": "dgx_host::edge_mlp2_backward(Tensor dout, Tensor[] saved, Tensor w1, Tensor w2",
         "knn_timing": "dgx_host::knn_timing(bool on) -> float[]",
+        "gemm_xwt": "dgx_host::gemm_xwt(Tensor x, Tensor w, Tensor(a!)? out, bool stats, bool out_bf16",
+        "gemm_xw": "dgx_host::gemm_xw(Tensor x, Tensor w, Tensor(a!)? out, bool accumulate)",
+        "gemm_atb": "dgx_host::gemm_atb(Tensor a, Tensor b, Tensor(c!) out, int split_rows, bool lds, int slab_cap_mb)",
+        "gemm32": "dgx_host::gemm32(Tensor a, Tensor b, Tensor(c!)? out, bool accumulate, Tensor? addend)",
+        "gemm_edge_dz_ok": "dgx_host::gemm_edge_dz_ok(Tensor dpq16, int cin) -> bool",
+        "weight_prep": "dgx_host::weight_prep(Tensor[] weights, int[] rows, int[] cols, bool[] stacked, bool[] split",
+        "weight_prep_one": "dgx_host::weight_prep_one(Tensor w, int rows, int cols, bool stacked)",
     }
     for name, head in want.items():
         assert str(getattr(torch.ops.dgx_host, name).default._schema).startswith(head), name
@@ -114,6 +121,52 @@ def test_schedule_layout_named_once(monkeypatch):
     assert S.opts() == 0 and S.opts(split=True) == 1 << bits.index("SPLIT32")
     monkeypatch.setattr(G, "SLAB_CAP_MB", 8)
     assert S.opts() == 8 << 8
+
+
+@pytest.mark.parametrize("fn,bk", [("dgx_gemm_slabs", 32), ("dgx_gemm_lds_slabs", 64), ("dgx_gemm_f32_slabs", 16)])
+def test_split_k_slab_counts(fn, bk):
+    """The slabs a split-K launch writes — what the launcher's grid, the slab
+    allocation and dgx_slab_reduce_f32's S all take from one function per GEMM
+    family: ceil(K / kchunk), kchunk = ceil(K / splits) rounded up to the
+    kernel's K-step; fewer than ``splits`` when K is short; 1 for K = 0."""
+    from dgx import _native
+    count = getattr(_native.lib(), fn)
+    for splits in (1, 2, 3, 7, 17, 128, 512):
+        assert count(0, splits) == 1
+        for K in (1, bk - 1, bk, bk + 1, 100, 2047, 2048, 4099, 32768):
+            chunk = -(-K // splits)
+            kchunk = -(-chunk // bk) * bk
+            assert count(K, splits) == -(-K // kchunk), (K, splits)
+    assert count(100, 0) == 1 and count(-5, 3) == 1
+    # a short K: 7 splits asked, one 64-deep K-step per slab, so fewer slabs written
+    assert _native.lib().dgx_gemm_lds_slabs(100, 7) == 2
+
+
+def test_weight_prep_layout_matches_schedule():
+    """gemm.prep_layout (plain Python: dynamo and torch.export trace through
+    it) restates the layout of the C++ schedule's weight-prep buffer; the
+    host-only dgx_host::weight_prep_layout reports the C++ one."""
+    from dgx import gemm as G, host
+    host.load()
+    T, F = True, False
+
+    def both(shapes):
+        total, lay = G.prep_layout(shapes)
+        ctotal, nt_off, nt_shape, tn_off, tn_shape = torch.ops.dgx_host.weight_prep_layout(
+            *(list(f) for f in zip(*shapes)))
+        assert ctotal == total
+        for j, (o1, s1, o2, s2) in enumerate(lay):
+            assert (nt_off[j], tuple(nt_shape[2 * j:2 * j + 2])) == (o1, s1)
+            assert (tn_off[j], tuple(tn_shape[2 * j:2 * j + 2])) == (o2, s2)
+            assert o1 % 8 == 0 and o2 % 8 == 0
+        return total, [(o1, o2) for (o1, _, o2, _) in lay], [s1 for (_, s1, _, _) in lay]
+
+    total, offs, nt = both([(64, 64, T, T), (128, 64, T, T), (256, 128, T, T), (1024, 512, F, F)])   # DGCNN
+    assert total == 1318912
+    assert offs == [(0, 16384), (24576, 57344), (73728, 204800), (270336, 794624)]
+    assert nt == [(128, 128), (256, 128), (512, 256), (1024, 512)]
+    total, offs, _ = both([(40, 24, F, F), (5, 3, T, T)])   # unaligned sizes: padded to 8 elements
+    assert (total, offs) == (2016, [(0, 960), (1920, 1984)])
 
 
 def test_knn_shape_routing():

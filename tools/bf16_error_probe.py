@@ -3,8 +3,8 @@
 Runs DGCNN(emb 1024) train fwd+bwd at B 32, N 1024, k 20 in bf16 mode and
 compares against the fp64 oracle routed by the engine's decisions (on the GPU
 in float64): the error of each block's output (the concat buffer) and of the
-final output/gradients, for the product path and for variants selected by
-``--variant``. Diagnostic only (tools/), not a test.
+final output/gradients, for the product path. Diagnostic only (tools/), not a
+test.
 """
 import argparse
 import os
@@ -32,61 +32,7 @@ def main():
     ap.add_argument("--B", type=int, default=32)
     ap.add_argument("--N", type=int, default=1024)
     ap.add_argument("--emb", type=int, default=1024)
-    ap.add_argument("--z32", action="store_true", help="store conv5's Z in fp32 instead of bf16")
-    ap.add_argument("--wexact", choices=["none", "edge", "conv5", "both"], default="none",
-                    help="forward GEMMs with the fp32 (unrounded) weight: emulates a hi+lo bf16 weight split")
     a = ap.parse_args()
-    from dgx import gemm as G0
-    if a.wexact != "none":
-        orig_prep_many, orig_prep_one, orig_lds = G0.prep_weights, G0.prep_weight, G0.lds_xwt
-        from dgx.edgeconv import split_weight
-
-        def tag(nt, w, rows, cols, stacked):
-            nt.w32 = split_weight(w, cols, rows) if stacked else w.reshape(rows, cols)
-            return nt
-
-        def prep_weights(jobs):
-            out = orig_prep_many(jobs)
-            res = []
-            for (w, r, c, st), (nt, tn) in zip(jobs, out):
-                want = (st and a.wexact in ("edge", "both")) or (not st and a.wexact in ("conv5", "both"))
-                res.append((tag(nt, w, r, c, st) if want else nt, tn))
-            return res
-
-        def lds_xwt(x16, w16, *args, **kw):
-            if hasattr(w16, "w32") and not args and not kw.get("accumulate") and kw.get("addend") is None:
-                z = torch.mm(x16.float(), w16.w32.t())
-                if kw.get("stats"):
-                    part = torch.stack([z.sum(0), (z * z).sum(0)]).unsqueeze(0).contiguous()
-                    return (z.to(torch.bfloat16) if kw.get("out_bf16") else z), part
-                return z
-            return orig_lds(x16, w16, *args, **kw)
-
-        class _GE:
-            def __getattr__(self, n):
-                return getattr(G0, n)
-        ge = _GE()
-        ge.prep_weights = prep_weights
-        ge.lds_xwt = lds_xwt
-        import dgx.pointconv as P0
-        import models.dgcnn as MD
-        E.G = ge
-        P0.G = ge
-        MD._gemm = ge
-    if a.z32:
-        from dgx import pointconv as P
-        G = P.G
-        orig = G.lds_xwt
-
-        class _G:
-            def __getattr__(self, n):
-                return getattr(G, n)
-
-            @staticmethod
-            def lds_xwt(*args, **kw):
-                kw["out_bf16"] = False
-                return orig(*args, **kw)
-        P.G = _G()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     k = 20
