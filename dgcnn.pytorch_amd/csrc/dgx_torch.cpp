@@ -1187,7 +1187,9 @@ Tensor pointconv_forward_impl(const Dev& d, const Tensor& X_in, const Tensor& X1
   const bool use_batch = ly.bn.use_batch();
   Tensor Z, gemm_part, Xop = X, xhi, xlo;
   if (bf16) {
-    if (X16.defined() && X16.numel() && lds_ok(X16, K)) {
+    // the LDS-DMA GEMMs take conv5 only when its backward fits them too: dX = dZ W has Co as
+    // its inner dimension (whole 64-wide K-steps) and dW = dZ^T X has Co output rows
+    if (X16.defined() && X16.numel() && lds_ok(X16, K) && Co % 64 == 0) {
       Xop = X16;
       if (!nt.defined() || !nt.numel()) {
         std::tie(nt, tn) = prep_weight(d, W, Co, (int)K);

@@ -365,8 +365,10 @@ torch.library.register_autograd("dgx::edgeconv_chain", _chain_bwd, setup_context
 _PC_KEPT = ("Z", "scale", "shift", "mean", "invstd")
 
 
-def _pc_lds(bf16, X16, K):
-    return bf16 and X16.numel() > 0 and K % 64 == 0
+def _pc_lds(bf16, X16, K, Co):
+    """Whether conv5 runs on the LDS-DMA GEMMs (pointconv_forward_impl's rule:
+    the backward's GEMMs have Co as inner dimension / output rows)."""
+    return bf16 and X16.numel() > 0 and K % 64 == 0 and Co % 64 == 0
 
 
 def _pc_prep(prep, Co, K):
@@ -398,7 +400,7 @@ def _(X, X16, B, N, weight, gamma, beta, running_mean, running_var, nbt, trainin
       bf16, prep, opts):
     M, K = X.shape
     Co = weight.shape[0]
-    z16 = _pc_lds(bf16, X16, K) and _use_batch(training, running_mean)
+    z16 = _pc_lds(bf16, X16, K, Co) and _use_batch(training, running_mean)
     kept = [X.new_empty((M, Co), dtype=_BF16 if z16 else _F32) if f == "Z" else X.new_empty((Co,), dtype=_F32)
             for f in _PC_KEPT]
     return (X.new_empty((B, Co, N), dtype=_F32), torch.empty_like(running_mean), torch.empty_like(running_var),
@@ -411,7 +413,7 @@ def pointconv_backward(dout: Tensor, X: Tensor, X16: Tensor, weight: Tensor, sav
                        opts: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     M, K = X.shape
     Co = weight.shape[0]
-    lds = _pc_lds(bf16, X16, K)
+    lds = _pc_lds(bf16, X16, K, Co)
     e16 = torch.empty(0, dtype=_BF16, device=X.device)
     nt, tn = (_pc_prep(prep, Co, K) if lds else (None, None))
     if lds and nt is None:

@@ -48,7 +48,9 @@ def pointconv_bn_lrelu(X, B, N, seq, training=None, X16=None, wprep=None):
     """X (B*N, K) point-major -> (B, Co, N) = LeakyReLU(BN(Conv1x1(X))) with the
     modules of ``seq`` = nn.Sequential(Conv2d(K,Co,1,bias=False) or Conv1d,
     BatchNorm2d/1d, LeakyReLU) (reference dgcnn.py:74-78). ``X16``: optional bf16 twin of X
-    (the GEMM operand in bf16). ``wprep``: optional bf16 (W, W^T) of the conv
+    (the GEMM operand in bf16; the LDS-DMA GEMMs take it when K and Co are
+    multiples of 64, any other width runs the register-staged bf16 GEMMs on
+    X). ``wprep``: optional bf16 (W, W^T) of the conv
     weight already made for this step (gemm.prep_weights). GEMM precision:
     ``precision.effective()`` at entry (bf16 mode or fp16/bf16 autocast ->
     bf16 MFMA). ``training`` is accepted for call compatibility only (dgx.bn:
