@@ -176,14 +176,33 @@ __device__ __forceinline__ void store_row4(float* __restrict__ p, int64_t rowbas
 // the per-thread 16-B reads of rows 4pg+i are bank-conflict-free.
 constexpr int ZT_LD = 72;  // bf16 per LDS row (64 + 8 pad)
 
+// Block order. A grid is (point blocks, channel blocks) and workgroups are
+// dispatched with blockIdx.x fastest; tile_map turns the dispatch index into
+// the (point block bt, channel block cb) this workgroup handles: cloud by
+// cloud, and inside a cloud (per_cloud point blocks) the point blocks fastest.
+// The workgroups that run together then cover whole (b, c, :) rows of dout /
+// out and all the point-major Z / dZ rows of a few clouds, where the launch
+// order spreads them over every cloud at a 64-channel width. rev walks the
+// same order backwards: the dz pass runs against the stats pass, so what the
+// stats pass read last is what the dz pass reads first.
+__device__ __forceinline__ void tile_map(int per_cloud, bool rev, int& bt, int& cb) {
+    const int gx = gridDim.x, gy = gridDim.y;
+    int id = blockIdx.y * gx + blockIdx.x;
+    if (rev) id = gx * gy - 1 - id;
+    const int per = per_cloud * gy, cloud = id / per, r = id - cloud * per;
+    cb = r / per_cloud;
+    bt = cloud * per_cloud + (r - cb * per_cloud);
+}
+
 struct ZTile {
     int b, n0, o0, pg, cg;
-    __device__ __forceinline__ explicit ZTile(int N) {
+    __device__ __forceinline__ explicit ZTile(int N, bool rev = false) {
         const int nt = (N + RT_P - 1) / RT_P;
-        const int bt = blockIdx.x;
+        int bt, cb;
+        tile_map(nt, rev, bt, cb);
         b = bt / nt;
         n0 = (bt - b * nt) * RT_P;
-        o0 = blockIdx.y * 64;
+        o0 = cb * 64;
         const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
         pg = lane & 31;
         cg = 2 * w + (lane >> 5);
@@ -193,19 +212,76 @@ struct ZTile {
 __device__ __forceinline__ int zt_off(int row, int chunk) { return row * ZT_LD + ((chunk ^ ((row >> 2) & 7)) << 3); }
 
 // rows [n0, n0+128) x channels [o0, o0+64) of Z into zt (zeros outside)
-__device__ __forceinline__ void stage_ztile(const bf16* __restrict__ Z, int b, int n0, int o0, int N, int C,
-                                            bf16* zt) {
-    for (int e = threadIdx.x; e < RT_P * 8; e += 256) {
+// in two halves: a thread loads its 4 of the 1024 16-B pieces into registers,
+// all four in flight together (and beside the dout loads issued before them),
+// then writes them to zt. As one load-wait-write loop the pieces went one
+// memory round trip after the other.
+constexpr int ZT_Q = RT_P * 8 / 256;
+
+// the tile lies inside the tensors and every 16-B access of it is aligned
+__device__ __forceinline__ bool tile_is_whole(int n0, int o0, int N, int C) {
+    return n0 + RT_P <= N && o0 + 64 <= C && (C % 8) == 0 && (N % 4) == 0;
+}
+
+template <bool FAST = true>
+__device__ __forceinline__ void load_ztile(const bf16* __restrict__ Z, int b, int n0, int o0, int N, int C,
+                                           bf16x8 (&v)[ZT_Q]) {
+    if (FAST && tile_is_whole(n0, o0, N, C)) {  // block-uniform: straight-line loads, nothing to decide per lane
+#pragma unroll
+        for (int q = 0; q < ZT_Q; ++q) {
+            const int e = threadIdx.x + 256 * q;
+            v[q] = *reinterpret_cast<const bf16x8*>(Z + ((int64_t)b * N + n0 + (e >> 3)) * C + o0 + 8 * (e & 7));
+        }
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < ZT_Q; ++q) {
+        const int e = threadIdx.x + 256 * q;
         const int row = e >> 3, ch = e & 7;
         const int n = n0 + row, o = o0 + 8 * ch;
-        bf16x8 v;
         if (n < N && o + 8 <= C && (C % 8) == 0) {
-            v = *reinterpret_cast<const bf16x8*>(Z + ((int64_t)b * N + n) * C + o);
+            v[q] = *reinterpret_cast<const bf16x8*>(Z + ((int64_t)b * N + n) * C + o);
         } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (n < N && o + j < C) ? Z[((int64_t)b * N + n) * C + o + j] : (bf16)0.f;
+            for (int j = 0; j < 8; ++j)
+                v[q][j] = (n < N && o + j < C) ? Z[((int64_t)b * N + n) * C + o + j] : (bf16)0.f;
         }
-        *reinterpret_cast<bf16x8*>(zt + zt_off(row, ch)) = v;
+    }
+}
+
+__device__ __forceinline__ void store_ztile(bf16* zt, const bf16x8 (&v)[ZT_Q]) {
+#pragma unroll
+    for (int q = 0; q < ZT_Q; ++q) {
+        const int e = threadIdx.x + 256 * q;
+        *reinterpret_cast<bf16x8*>(zt + zt_off(e >> 3, e & 7)) = v[q];
+    }
+}
+
+__device__ __forceinline__ void stage_ztile(const bf16* __restrict__ Z, int b, int n0, int o0, int N, int C,
+                                            bf16* zt) {
+    bf16x8 v[ZT_Q];
+    load_ztile(Z, b, n0, o0, N, C, v);
+    store_ztile(zt, v);
+}
+
+// dout(b, o0 + 8cg + j, n .. n+3), n = n0 + 4pg, j = 0..7 (zeros outside)
+template <bool FAST = true>
+__device__ __forceinline__ void load_g48(const float* __restrict__ dout, int b, int n0, int o0, int pg, int cg, int N,
+                                         int C, float (&g)[8][4]) {
+    const int n = n0 + 4 * pg;
+    if (FAST && tile_is_whole(n0, o0, N, C)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float4 v = *reinterpret_cast<const float4*>(dout + ((int64_t)b * C + o0 + 8 * cg + j) * N + n);
+            g[j][0] = v.x; g[j][1] = v.y; g[j][2] = v.z; g[j][3] = v.w;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int oo = o0 + 8 * cg + j;
+        const float4 v = load_row4(dout, ((int64_t)b * C + oo) * N, n, N, oo < C);
+        g[j][0] = v.x; g[j][1] = v.y; g[j][2] = v.z; g[j][3] = v.w;
     }
 }
 
@@ -244,30 +320,30 @@ __global__ __launch_bounds__(256) void apply16_lt_kernel(const bf16* __restrict_
 
 // PASS 1 of the BN backward with the transposed tile: dZ = a d + c0 + c1 z,
 // d = dout * LeakyReLU'(a z + b); dZ goes back through the LDS tile so the
-// point-major bf16 rows are written as 16-B pieces.
+// point-major bf16 rows are written as 16-B pieces. Walks the tiles in the
+// reverse of PASS 0's order.
 __global__ __launch_bounds__(256) void bwd16_dz_lt_kernel(const float* __restrict__ dout, const bf16* __restrict__ Z,
                                                           int N, int C, const float* __restrict__ scale,
                                                           const float* __restrict__ shift, float slope,
                                                           const float* __restrict__ c0, const float* __restrict__ c1,
                                                           bf16* __restrict__ dZ) {
     __shared__ __attribute__((aligned(16))) bf16 zt[RT_P * ZT_LD];
-    const ZTile T(N);
-    const int n = T.n0 + 4 * T.pg;
-    float g[8][4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int oo = T.o0 + 8 * T.cg + j;
-        const float4 v = load_row4(dout, ((int64_t)T.b * C + oo) * N, n, N, oo < C);
-        g[j][0] = v.x; g[j][1] = v.y; g[j][2] = v.z; g[j][3] = v.w;
+    __shared__ __attribute__((aligned(16))) float4 cst[64];   // per channel {scale, shift, c0, c1}
+    const ZTile T(N, true);
+    if (threadIdx.x < 64) {  // read before the tile's barrier, so no load stands between the tile and its use
+        const int oj = min(T.o0 + (int)threadIdx.x, C - 1);
+        cst[threadIdx.x] = make_float4(scale[oj], shift[oj], c0[oj], c1[oj]);
     }
+    float g[8][4];
+    load_g48(dout, T.b, T.n0, T.o0, T.pg, T.cg, N, C, g);
     stage_ztile(Z, T.b, T.n0, T.o0, N, C, zt);
     __syncthreads();
     float z[4][8];
     read_z48(zt, T.pg, T.cg, z);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int oo = min(T.o0 + 8 * T.cg + j, C - 1);
-        const float a = scale[oo], sh = shift[oo], k0 = c0[oo], k1 = c1[oo];
+        const float4 k4 = cst[8 * T.cg + j];
+        const float a = k4.x, sh = k4.y, k0 = k4.z, k1 = k4.w;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float d = g[j][i] * (fmaf(a, z[i][j], sh) > 0.f ? 1.f : slope);
@@ -298,8 +374,9 @@ __global__ __launch_bounds__(256) void bwd16_dz_lt_kernel(const float* __restric
 }
 
 // PASS 0 with the transposed tile over RS_LT consecutive 128-point tiles per
-// block: per-thread sums over its 4 points, then over the 32 lanes of its
-// channel group (one shuffle tree), one partial row per block.
+// block: per-thread sums over its 4 points, tile after tile, then over the 32
+// lanes of its channel group (one shuffle tree), one partial row per
+// 256-point block (bt, whichever workgroup the block order gives it to).
 constexpr int RS_LT = 2;
 __global__ __launch_bounds__(256, 4) void bwd16_stats_lt_kernel(const float* __restrict__ dout,
                                                              const bf16* __restrict__ Z, int N, int C,
@@ -311,9 +388,11 @@ __global__ __launch_bounds__(256, 4) void bwd16_stats_lt_kernel(const float* __r
     __shared__ __attribute__((aligned(16))) bf16 zt[RT_P * ZT_LD];
     __shared__ __attribute__((aligned(16))) float4 cst[64];   // per channel {scale, shift, mean, invstd}
     const int nt = (N + RT_P * RS_LT - 1) / (RT_P * RS_LT);
-    const int b = blockIdx.x / nt;
-    const int nb = (blockIdx.x - b * nt) * RT_P * RS_LT;
-    const int o0 = blockIdx.y * 64;
+    int bt, cb;
+    tile_map(nt, false, bt, cb);
+    const int b = bt / nt;
+    const int nb = (bt - b * nt) * RT_P * RS_LT;
+    const int o0 = cb * 64;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int pg = lane & 31, cg = 2 * w + (lane >> 5);
     if (threadIdx.x < 64) {
@@ -327,32 +406,38 @@ __global__ __launch_bounds__(256, 4) void bwd16_stats_lt_kernel(const float* __r
         s1[j] = 0.f;
         s2[j] = 0.f;
     }
-#pragma unroll 1
+    // The loads keep their per-lane guards here (FAST = false), and a tile's
+    // loads follow the previous tile's sums in program order: the compiler
+    // then starts them under those sums as far as 128 VGPRs allow. With the
+    // straight-line whole-tile loads it hoists all of them and spills
+    // (128 VGPRs + 132 B of scratch).
+    float g[8][4];
+    bf16x8 zr[ZT_Q];
+    load_g48<false>(dout, b, nb, o0, pg, cg, N, C, g);
+    load_ztile<false>(Z, b, nb, o0, N, C, zr);
+#pragma unroll
     for (int it = 0; it < RS_LT; ++it) {
         const int n0 = nb + it * RT_P;
-        if (n0 >= N) break;
-        const int n = n0 + 4 * pg;
-        float g[8][4];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int oo = o0 + 8 * cg + j;
-            const float4 v = load_row4(dout, ((int64_t)b * C + oo) * N, n, N, oo < C);
-            g[j][0] = v.x; g[j][1] = v.y; g[j][2] = v.z; g[j][3] = v.w;
-        }
-        if (it > 0) __syncthreads();  // previous tile's reads done (a barrier here would also wait for the dout loads)
-        stage_ztile(Z, b, n0, o0, N, C, zt);
+        if (it > 0) __syncthreads();  // previous tile's reads done
+        store_ztile(zt, zr);
         __syncthreads();
-        float z[4][8];
-        read_z48(zt, pg, cg, z);
+        if (n0 < N) {
+            float z[4][8];
+            read_z48(zt, pg, cg, z);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float4 k4 = cst[8 * cg + j];
+            for (int j = 0; j < 8; ++j) {
+                const float4 k4 = cst[8 * cg + j];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float d = g[j][i] * (fmaf(k4.x, z[i][j], k4.y) > 0.f ? 1.f : slope);
-                s1[j] += d;
-                s2[j] = fmaf(d, (z[i][j] - k4.z) * k4.w, s2[j]);
+                for (int i = 0; i < 4; ++i) {
+                    const float d = g[j][i] * (fmaf(k4.x, z[i][j], k4.y) > 0.f ? 1.f : slope);
+                    s1[j] += d;
+                    s2[j] = fmaf(d, (z[i][j] - k4.z) * k4.w, s2[j]);
+                }
             }
+        }
+        if (it + 1 < RS_LT) {  // the next tile (past N its loads touch nothing)
+            load_g48<false>(dout, b, n0 + RT_P, o0, pg, cg, N, C, g);
+            load_ztile<false>(Z, b, n0 + RT_P, o0, N, C, zr);
         }
     }
 #pragma unroll
@@ -368,8 +453,8 @@ __global__ __launch_bounds__(256, 4) void bwd16_stats_lt_kernel(const float* __r
         for (int j = 0; j < 8; ++j) {
             const int oo = o0 + 8 * cg + j;
             if (oo < C) {
-                partials[(int64_t)blockIdx.x * 2 * C + oo] = s1[j];
-                partials[(int64_t)blockIdx.x * 2 * C + C + oo] = s2[j];
+                partials[(int64_t)bt * 2 * C + oo] = s1[j];
+                partials[(int64_t)bt * 2 * C + C + oo] = s2[j];
             }
         }
     }
