@@ -26,7 +26,10 @@
 //   gemm_xwt / gemm_xw / gemm_atb / gemm32 / gemm_edge_dz_ok / weight_prep / weight_prep_one
 //                                         the schedule's GEMM and weight-prep helpers, one op each (dgx.gemm)
 //   weight_prep_layout                    the weight-prep buffer's layout, host only (dgx.gemm.prep_layout restates it)
+//   knn / knn_image_buffers               the kNN dispatch the chain runs too, and its prepared-operand scratch
 //   knn_timing                            per-thread HIP-event timing of the kNN selection launches
+//   reverse_graphs                        CSR in-edge lists of kNN graphs, 8 graphs per launch
+//   graph_feature / graph_feature_backward get_graph_feature's edge tensor after the kNN, and its gradient
 //   layout                                the name tables of the saved-state lists and the opts word
 //                                         (dgx.schedule names the same fields: one layout, checked by a test)
 #include <ATen/ATen.h>
@@ -37,6 +40,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <optional>
@@ -55,8 +59,6 @@ using torch::autograd::variable_list;
 
 constexpr int kEpiStore = 0, kEpiAccum = 1, kEpiStats = 2, kEpiSlab = 3, kEpiStats16 = 4;
 constexpr int kSmallKMax = 16;                                   // dgx.gemm.SMALLK_MAX
-constexpr int kFastMaxC = 128, kFastMaxK = 64, kFastMaxN = 12288;  // csrc/knn.hip's fused kernel
-constexpr int kGenericMaxK = 8192;                               // csrc/knn_generic.hip
 
 void check(int rc, const char* what) {
   TORCH_CHECK(rc == 0, "dgx: ", what, " failed (", rc, ": ", dgx_strerror(rc), ")");
@@ -619,12 +621,10 @@ std::pair<Tensor, std::vector<std::pair<Tensor, Tensor>>> prep_weights(const Dev
 }
 
 // ------------------------------------------------------------------- kNN ----
-bool fast_shape(int C, int k, int N) { return C <= kFastMaxC && k <= kFastMaxK && N <= kFastMaxN; }
-
-// dgx.ops.knn_image_buffers
-std::pair<Tensor, Tensor> knn_image_buffers(const Dev& d, int B, int C, int N) {
+// (xx, image) scratch of one fused-kernel kNN call: dgx_knn_prepare_f32's outputs, or a producer kernel's
+std::pair<Tensor, Tensor> knn_image_buffers(const at::TensorOptions& f32, int B, int C, int N) {
   const size_t img_bytes = dgx_knn_image_bytes(B, C, N);
-  return {at::empty({(int64_t)B * N}, d.f32), at::empty({(int64_t)((std::max<size_t>(img_bytes, 4) + 3) / 4)}, d.f32)};
+  return {at::empty({(int64_t)B * N}, f32), at::empty({(int64_t)((std::max<size_t>(img_bytes, 4) + 3) / 4)}, f32)};
 }
 
 // the reference's sum(x**2, dim=1) rounding order for x's strides (dgx.ops.reduction_order)
@@ -632,32 +632,41 @@ int reduction_order(const Tensor& x) {
   return (x.size(1) > 1 && x.size(2) > 1 && x.stride(1) < x.stride(2)) ? DGX_ORDER_VEC8X4 : DGX_ORDER_STRIDED;
 }
 
-// dgx.ops.knn_raw: int32 (B,N,k) ids of a (B,C,N) fp32 view; prepared: |x|^2 + image already written
-Tensor knn32(const Dev& d, const Tensor& xv, int k, int order, const std::pair<Tensor, Tensor>* prepared) {
+// The kNN dispatch: (ids (B,N,k) of type `ids`, the selected values or an undefined tensor) of a (B,C,N) fp32
+// view. The fused kernel unless the shape or `generic` asks for the other; prepared: its |x|^2 + operand image,
+// already written. Every check comes before the first allocation or launch.
+std::pair<Tensor, Tensor> knn(const Dev& d, const Tensor& xv, int k, int order, at::ScalarType ids, bool values,
+                              bool generic, const std::pair<Tensor, Tensor>* prepared) {
   const int B = (int)xv.size(0), C = (int)xv.size(1), N = (int)xv.size(2);
   TORCH_CHECK(k >= 1 && k <= N, "knn: selected index k out of range (k=", k, ", N=", N, ")");
-  Tensor idx = at::empty({B, N, k}, d.i32);
-  if (!fast_shape(C, k, N)) {   // the generic kernel: same values, same canonical order
-    TORCH_CHECK(!prepared, "knn: prepared operands exist for the fused kernel's shapes only");
-    TORCH_CHECK(k <= kGenericMaxK, "dgx knn: k = ", k, " > ", kGenericMaxK, " neighbours");
+  generic = generic || !dgx_knn_fast_shape(C, k, N);
+  TORCH_CHECK(!(generic && prepared), "knn: prepared operands exist for the fused kernel's shapes only");
+  TORCH_CHECK_NOT_IMPLEMENTED(!generic || k <= dgx_knn_generic_max_k(), "dgx knn: k = ", k, " > ",
+                              dgx_knn_generic_max_k(), " neighbours");
+  const size_t img_bytes = generic ? 0 : dgx_knn_image_bytes(B, C, N);
+  TORCH_CHECK(!prepared || (prepared->first.numel() == (int64_t)B * N &&
+                            (size_t)prepared->second.numel() * 4 >= img_bytes),
+              "knn: prepared |x|^2 / image buffers do not match the cloud");
+  Tensor idx = at::empty({B, N, k}, ids == at::kLong ? d.i64 : d.i32);
+  Tensor vals = values ? at::empty({B, N, k}, d.f32) : Tensor();
+  int64_t* i64 = ids == at::kLong ? P<int64_t>(idx) : nullptr;
+  int32_t* i32 = ids == at::kLong ? nullptr : P<int32_t>(idx);
+  if (generic) {   // same values, same canonical order; a view with neither inner stride 1 is read from a copy
     Tensor x = xv;
     if (x.stride(2) != 1 && x.stride(1) != 1) x = x.contiguous();
     const size_t ws_bytes = dgx_knn_generic_workspace_bytes(B, C, N);
     Tensor ws = at::empty({(int64_t)((ws_bytes + 3) / 4)}, d.f32);
-    check(dgx_knn_generic_f32(P(x), x.stride(0), x.stride(1), x.stride(2), B, C, N, k, order, nullptr, P<int32_t>(idx),
-                              nullptr, P(ws), ws_bytes, d.stream),
+    check(dgx_knn_generic_f32(P(x), x.stride(0), x.stride(1), x.stride(2), B, C, N, k, order, i64, i32, P(vals),
+                              P(ws), ws_bytes, d.stream),
           "knn (generic)");
-    return idx;
+    return {idx, vals};
   }
-  const size_t img_bytes = dgx_knn_image_bytes(B, C, N);
-  std::pair<Tensor, Tensor> bufs;
   const float* xp = static_cast<const float*>(xv.data_ptr());
+  std::pair<Tensor, Tensor> bufs;
   if (prepared) {
     bufs = *prepared;
-    TORCH_CHECK(bufs.first.numel() == (int64_t)B * N && (size_t)bufs.second.numel() * 4 >= img_bytes,
-                "knn: prepared |x|^2 / image buffers do not match the cloud");
-  } else {
-    bufs = knn_image_buffers(d, B, C, N);
+  } else {   // |x|^2 and the MFMA operand image in one pass over x
+    bufs = knn_image_buffers(d.f32, B, C, N);
     check(dgx_knn_prepare_f32(xp, xv.stride(0), xv.stride(1), xv.stride(2), B, C, N, order, P(bufs.first),
                               P(bufs.second), img_bytes, d.stream),
           "knn prepare");
@@ -668,8 +677,8 @@ Tensor knn32(const Dev& d, const Tensor& xv, int k, int order, const std::pair<T
     (void)hipEventCreate(&rec.e1);
     (void)hipEventRecord(rec.e0, static_cast<hipStream_t>(d.stream));
   }
-  check(dgx_knn_select_f32(xp, xv.stride(0), xv.stride(1), xv.stride(2), P(bufs.first), B, C, N, k, nullptr,
-                           P<int32_t>(idx), nullptr, P(bufs.second), img_bytes, d.stream),
+  check(dgx_knn_select_f32(xp, xv.stride(0), xv.stride(1), xv.stride(2), P(bufs.first), B, C, N, k, i64, i32, P(vals),
+                           P(bufs.second), img_bytes, d.stream),
         "knn");
   if (t_knn_timing) {
     (void)hipEventRecord(rec.e1, static_cast<hipStream_t>(d.stream));
@@ -680,7 +689,30 @@ Tensor knn32(const Dev& d, const Tensor& xv, int k, int order, const std::pair<T
     rec.k = k;
     t_knn_recs.push_back(rec);
   }
-  return idx;
+  return {idx, vals};
+}
+
+// Reverse kNN graphs (CSR of in-edges: rowptr (M+1), edges (M k)) of same-shaped int32 (B,N,k) graphs, 8 per
+// launch (dgx_graph_reverse_multi's limit): the graphs' workgroups share the chip
+std::pair<std::vector<Tensor>, std::vector<Tensor>> reverse_graphs(const Dev& d, const std::vector<Tensor>& idxs, int B,
+                                                                   int N, int k) {
+  const int n = (int)idxs.size();
+  const int64_t M = (int64_t)B * N;
+  std::vector<Tensor> rowptr(n), edges(n);
+  for (int base = 0; base < n; base += 8) {
+    const int m = std::min(8, n - base);
+    std::vector<const int32_t*> ip(m);
+    std::vector<int32_t*> rp(m), ep(m);
+    for (int j = 0; j < m; ++j) {
+      rowptr[base + j] = at::empty({M + 1}, d.i32);
+      edges[base + j] = at::empty({M * k}, d.i32);
+      ip[j] = P<int32_t>(idxs[base + j]);
+      rp[j] = P<int32_t>(rowptr[base + j]);
+      ep[j] = P<int32_t>(edges[base + j]);
+    }
+    check(dgx_graph_reverse_multi(m, ip.data(), B, N, k, rp.data(), ep.data(), d.stream), "reverse graphs");
+  }
+  return {rowptr, edges};
 }
 
 // --------------------------------------------------------- EdgeConv chain ----
@@ -807,13 +839,13 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
                     "dgx chain: idx0 must be contiguous int32 (B, N, k)");
         idx = idx0;
       } else {
-        idx = knn32(d, x, k, reduction_order(x), nullptr);
+        idx = knn(d, x, k, reduction_order(x), at::kInt, false, false, nullptr).first;
       }
     } else {
       X = r.xcat.narrow(1, off_in, cin);
       // blocks 2-4 see contiguous (B,C,N) features (max over dim -1), hence the strided order
       Tensor xv = r.xcat.as_strided({B, cin, N}, {N * total, 1, total}, r.xcat.storage_offset() + off_in);
-      idx = knn32(d, xv, k, DGX_ORDER_STRIDED, have_prepared ? &next_prepared : nullptr);
+      idx = knn(d, xv, k, DGX_ORDER_STRIDED, at::kInt, false, false, have_prepared ? &next_prepared : nullptr).first;
     }
     have_prepared = false;
     if (cin <= kSmallKMax) {
@@ -846,9 +878,9 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
             "edge gather");
       Stats st = use_batch ? batch_stats(d, partials, prow, count, ly.gamma, ly.beta, ly.bn)
                            : running_stats(d, ly.gamma, ly.beta, ly.bn);
-      if (o.fuse_image && li + 1 < n && (co == 64 || co == 128) && N % 32 == 0 && fast_shape(co, k, N)) {
+      if (o.fuse_image && li + 1 < n && (co == 64 || co == 128) && N % 32 == 0 && dgx_knn_fast_shape(co, k, N)) {
         // the apply also writes the next block's kNN |x|^2 and operand image
-        next_prepared = knn_image_buffers(d, B, co, N);
+        next_prepared = knn_image_buffers(d.f32, B, co, N);
         have_prepared = true;
         check(dgx_bn_lrelu_apply_knn_image_f32(P(ysel), B, N, co, P(st.scale), P(st.shift), (float)ly.slope, out,
                                                (int)total, out16, P(next_prepared.first), P(next_prepared.second),
@@ -916,28 +948,18 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
     dxcat = dxcat.clone();
   }
   std::vector<bool> selecting(n);
-  std::vector<const int32_t*> ids;
-  std::vector<Tensor> rowptr(n), edges(n);
+  std::vector<Tensor> idxs(n);
   for (int li = 0; li < n; ++li) {
-    const Tensor& idx = field(saved, li, kIdx);
-    selecting[li] = idx.numel() > 0;
+    idxs[li] = field(saved, li, kIdx);
+    selecting[li] = idxs[li].numel() > 0;
     TORCH_CHECK(selecting[li], "dgx chain backward: block ", li + 1, " ran without its backward state");
-    TORCH_CHECK(idx.scalar_type() == at::kInt && idx.is_contiguous(), "dgx: kNN ids must be contiguous int32");
+    TORCH_CHECK(idxs[li].scalar_type() == at::kInt && idxs[li].is_contiguous(),
+                "dgx: kNN ids must be contiguous int32");
   }
-  // reverse kNN graphs of every block in one launch (<= 8 per launch)
-  for (int base = 0; base < n; base += 8) {
-    const int m = std::min(8, n - base);
-    std::vector<const int32_t*> ip(m);
-    std::vector<int32_t*> rp(m), ep(m);
-    for (int j = 0; j < m; ++j) {
-      rowptr[base + j] = at::empty({M + 1}, d.i32);
-      edges[base + j] = at::empty({M * k}, d.i32);
-      ip[j] = P<int32_t>(field(saved, base + j, kIdx));
-      rp[j] = P<int32_t>(rowptr[base + j]);
-      ep[j] = P<int32_t>(edges[base + j]);
-    }
-    check(dgx_graph_reverse_multi(m, ip.data(), B, N, k, rp.data(), ep.data(), d.stream), "reverse graphs");
-  }
+  // reverse kNN graphs of every block, at the start of the backward on its stream (a build on a side stream
+  // overlapping the forward measured slower, 1.63 vs 1.56 ms/step at cfg2: the concurrent kernels contend for
+  // the L2 the kNN operand images live in)
+  const auto [rowptr, edges] = reverse_graphs(d, idxs, B, N, k);
   const double count = (double)M * k;
   // packed dz|slot words (18 significant bits of dz) in bf16 mode, and in the
   // fp32 mode whose conv5 GEMMs are split bf16 (2^-16 per product: the same
@@ -2012,6 +2034,90 @@ Tensor dgcnn(const Tensor& x, at::TensorList params, const c10::List<std::option
   return DgcnnFn::apply(x, params, bufs, idx0, c)[0];
 }
 
+// ---- kNN, reverse graphs and the graph feature as ops (dgx.ops binds them) ----
+// dgx_host::knn -> [ids] or [ids, values] (knn above); xx / image: prepared operands
+std::vector<Tensor> knn_op(const Tensor& x, int64_t k, int64_t order, at::ScalarType ids, bool values, bool generic,
+                           const std::optional<Tensor>& xx, const std::optional<Tensor>& image) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.scalar_type() == at::kFloat, "knn: a (B, C, N) fp32 device view expected");
+  TORCH_CHECK(ids == at::kInt || ids == at::kLong, "knn: ids are int32 or int64");
+  TORCH_CHECK(xx.has_value() == image.has_value() &&
+                  (!xx.has_value() || (xx->options().type_equal(x.options()) && image->options().type_equal(x.options()) &&
+                                       xx->device() == x.device() && image->device() == x.device())),
+              "knn: prepared operands are |x|^2 and the image, fp32 buffers on the cloud's device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Dev d(x);
+  std::pair<Tensor, Tensor> prepared;
+  if (xx.has_value()) prepared = {*xx, *image};
+  auto r = knn(d, x, (int)std::clamp<int64_t>(k, 0, INT32_MAX), (int)order, ids, values, generic,
+               xx.has_value() ? &prepared : nullptr);
+  return values ? std::vector<Tensor>{r.first, r.second} : std::vector<Tensor>{r.first};
+}
+
+std::tuple<Tensor, Tensor> knn_image_buffers_op(int64_t B, int64_t C, int64_t N, at::Device dev) {
+  auto r = knn_image_buffers(at::TensorOptions().device(dev).dtype(at::kFloat), (int)B, (int)C, (int)N);
+  return {r.first, r.second};
+}
+
+void check_ids(const Tensor& idx) {
+  TORCH_CHECK(idx.is_cuda() && idx.dim() == 3 && idx.scalar_type() == at::kInt && idx.is_contiguous(),
+              "dgx: kNN ids must be contiguous int32 (B, N, k)");
+}
+
+// dgx_host::reverse_graphs -> the graphs' rowptr tensors, then their edges tensors
+std::vector<Tensor> reverse_graphs_op(at::TensorList idxs) {
+  TORCH_CHECK(!idxs.empty(), "dgx reverse graphs: no graphs");
+  for (const auto& idx : idxs) {
+    check_ids(idx);
+    TORCH_CHECK(idx.sizes() == idxs[0].sizes() && idx.device() == idxs[0].device(),
+                "dgx reverse graphs: graphs of one shape on one device expected");
+  }
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(idxs[0].device());
+  auto r = reverse_graphs(Dev(idxs[0]), idxs.vec(), (int)idxs[0].size(0), (int)idxs[0].size(1), (int)idxs[0].size(2));
+  r.first.insert(r.first.end(), r.second.begin(), r.second.end());
+  return r.first;
+}
+
+// dgx_host::graph_feature -> get_graph_feature's edge tensor (dgcnn.py:15-44), contiguous in the layout of `mode`
+Tensor graph_feature(const Tensor& x, const Tensor& idx, int64_t mode) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.scalar_type() == at::kFloat, "graph_feature: (B, C, N) fp32 expected");
+  check_ids(idx);
+  const int64_t B = x.size(0), C = x.size(1), N = x.size(2), k = idx.size(2);
+  TORCH_CHECK(idx.size(0) == B && idx.size(1) == N && idx.device() == x.device(),
+              "graph_feature: ids do not match the cloud");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  Dev d(x);
+  const std::vector<int64_t> shape = mode == DGX_GF_KNN_ONLY ? std::vector<int64_t>{B, N, k, C}
+                                                             : std::vector<int64_t>{B, mode == DGX_GF_DISP ? C : 2 * C, N, k};
+  Tensor out = at::empty(shape, d.f32);
+  check(dgx_graph_feature_f32(P(x), x.stride(0), x.stride(1), x.stride(2), (int)B, (int)C, (int)N, P<int32_t>(idx),
+                              (int)k, (int)mode, P(out), d.stream),
+        "graph_feature");
+  return out;
+}
+
+// dgx_host::graph_feature_backward -> dx (B, C, N): the deterministic CSR pull where it takes the shape, else atomics
+Tensor graph_feature_backward(Tensor dout, const Tensor& idx, int64_t C, int64_t mode) {
+  check_ids(idx);
+  TORCH_CHECK(dout.device() == idx.device(), "graph_feature backward: gradient and ids on one device expected");
+  const int B = (int)idx.size(0), N = (int)idx.size(1), k = (int)idx.size(2);
+  TORCH_CHECK(C >= 1 && dout.numel() == idx.numel() * C * (mode == DGX_GF_CAT || mode == DGX_GF_DIFFCAT ? 2 : 1),
+              "graph_feature backward: gradient does not match the edge tensor of mode ", mode);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dout.device());
+  Dev d(dout);
+  dout = dout.contiguous().to(at::kFloat);
+  Tensor dx = at::zeros({B, C, N}, d.f32);
+  if (k <= 64 && (int64_t)B * N < ((int64_t)1 << 25)) {
+    const auto [rowptr, edges] = reverse_graphs(d, {idx}, B, N, k);
+    check(dgx_graph_feature_bwd_csr_f32(P(dout), B, (int)C, N, k, (int)mode, P<int32_t>(rowptr[0]), P<int32_t>(edges[0]),
+                                        P(dx), d.stream),
+          "graph_feature backward");
+  } else {
+    check(dgx_graph_feature_bwd_f32(P(dout), B, (int)C, N, P<int32_t>(idx), k, (int)mode, P(dx), d.stream),
+          "graph_feature backward");
+  }
+  return dx;
+}
+
 // dgx_host::knn_timing(on): on = true clears and starts recording this thread's kNN
 // selection launches; on = false stops and returns [ms, flops, B, C, N, k] per launch
 std::vector<double> knn_timing(bool on) {
@@ -2063,7 +2169,13 @@ TORCH_LIBRARY(dgx_host, m) {
         "str group, bool bf16, int opts) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("dgcnn(Tensor x, Tensor[] params, Tensor?[] bufs, float[] bn_f, int[] bn_i, str[] groups, Tensor? idx0, "
         "int k, bool bf16, int opts) -> Tensor");
+  m.def("knn(Tensor x, int k, int order, ScalarType ids, bool values, bool generic, Tensor? xx, Tensor? image) "
+        "-> Tensor[]");
+  m.def("knn_image_buffers(int B, int C, int N, Device device) -> (Tensor, Tensor)", &knn_image_buffers_op);
   m.def("knn_timing(bool on) -> float[]", &knn_timing);
+  m.def("reverse_graphs(Tensor[] idxs) -> Tensor[]");
+  m.def("graph_feature(Tensor x, Tensor idx, int mode) -> Tensor");
+  m.def("graph_feature_backward(Tensor dout, Tensor idx, int C, int mode) -> Tensor");
   m.def("edge_mlp2_forward(Tensor x, Tensor idx, int k, Tensor w1, Tensor g1, Tensor b1, Tensor w2, Tensor g2, "
         "Tensor b2, Tensor?[] bn_t, float[] bn_f, int[] bn_i, str[] groups, bool bf16, bool need_grad, "
         "bool fused_bwd) -> (Tensor, Tensor[])");
@@ -2108,4 +2220,8 @@ TORCH_LIBRARY_IMPL(dgx_host, CompositeExplicitAutograd, m) {
   m.impl("gemm_edge_dz_ok", gemm_edge_dz_ok);
   m.impl("weight_prep", weight_prep);
   m.impl("weight_prep_one", weight_prep_one);
+  m.impl("knn", knn_op);
+  m.impl("reverse_graphs", reverse_graphs_op);
+  m.impl("graph_feature", graph_feature);
+  m.impl("graph_feature_backward", graph_feature_backward);
 }

@@ -277,6 +277,9 @@ __global__ __launch_bounds__(256) void knn_image_kernel(const float* __restrict_
 inline int knn_nstep(int C) { return C <= 4 ? 1 : (C <= 12 ? 3 : (C <= 32 ? 8 : (C <= 64 ? 16 : 32))); }
 inline int knn_ntile(int N) { return (N + 15) / 16; }
 
+// the fused kernel's shapes (dgx_knn_fast_shape; everything else is csrc/knn_generic.hip's)
+constexpr int FIX_MAXC = 128;    // largest C (two cascade runs of |x|^2, NSTEP = 32)
+constexpr int FIX_MAXK = 64;     // largest k (dispatch_k's last tier)
 constexpr int FIX_MAXN = 12288;  // largest N (the fix-up's tie bitmap)
 constexpr int FX_CAP = 256;      // candidates above T0 ranked directly by the fix-up
 
@@ -1194,6 +1197,8 @@ extern "C" {
 void dgx_knn_stats_buffer(void* dev) { g_knn_stats = static_cast<uint32_t*>(dev); }
 #endif
 
+int dgx_knn_fast_shape(int C, int k, int N) { return C <= FIX_MAXC && k <= FIX_MAXK && N <= FIX_MAXN; }
+
 const char* dgx_knn_kernel_name(int C, int k, int N) {
     // the selection kernel dgx_knn_select_f32 launches for (C, k, N) on grids of at least
     // 512 workgroups (knn_small: fewer clouds keep one query group per wave), as profilers print it
@@ -1209,7 +1214,7 @@ const char* dgx_knn_kernel_name(int C, int k, int N) {
         }
     };
     static const Names names;  // thread-safe one-time initialisation
-    if (C < 1 || C > 128 || k < 1 || k > 64 || N < 1) return "";
+    if (C < 1 || C > FIX_MAXC || k < 1 || k > FIX_MAXK || N < 1) return "";
     const int ns = knn_nstep(C);
     const int a = ns == 1 ? 0 : ns == 3 ? 1 : ns == 8 ? 2 : ns == 16 ? 3 : 4;
     const int b = k <= 16 ? 0 : k <= 20 ? 1 : k <= 32 ? 2 : k <= 40 ? 3 : 4;
@@ -1218,7 +1223,7 @@ const char* dgx_knn_kernel_name(int C, int k, int N) {
 }
 
 int dgx_knn_query_groups(int B, int C, int k, int N) {
-    if (B < 1 || C < 1 || C > 128 || k < 1 || k > 64 || N < 1) return 0;
+    if (B < 1 || C < 1 || C > FIX_MAXC || k < 1 || k > FIX_MAXK || N < 1) return 0;
     const int kb = k <= 16 ? 16 : k <= 20 ? 20 : k <= 32 ? 32 : k <= 40 ? 40 : 64;   // dispatch_k's tiers
     return knn_groups_launched(knn_nstep(C), kb, B, N);
 }
@@ -1272,7 +1277,7 @@ size_t dgx_knn_workspace_bytes(int B, int C, int N) {
 int dgx_knn_prepare_f32(const float* x, int64_t sB, int64_t sC, int64_t sN, int B, int C, int N, int order,
                         float* xx, void* image, size_t image_bytes, void* stream) {
     if (!x || !xx || B < 0 || C < 1 || N < 1) return DGX_EINVAL;
-    if (C > 128) return DGX_EUNSUPPORTED;
+    if (C > FIX_MAXC) return DGX_EUNSUPPORTED;
     if (B == 0) return DGX_OK;
     if (!image || image_bytes < dgx_knn_image_bytes(B, C, N)) return DGX_EINVAL;
     if ((reinterpret_cast<uintptr_t>(image) & 15) != 0) return DGX_EINVAL;  // 16-byte operand loads
@@ -1295,7 +1300,7 @@ int knn_select(const float* x, int64_t sB, int64_t sC, int64_t sN, const float* 
                int64_t* idx64, int32_t* idx32, float* vals, const void* image, size_t image_bytes, void* stream) {
     if (!x || !xx || B < 0 || C < 1 || N < 1 || k < 1 || k > N) return DGX_EINVAL;
     if (!idx64 && !idx32) return DGX_EINVAL;
-    if (C > 128 || k > 64 || N > FIX_MAXN) return DGX_EUNSUPPORTED;
+    if (!dgx_knn_fast_shape(C, k, N)) return DGX_EUNSUPPORTED;
     if (B == 0) return DGX_OK;
     if (!image || image_bytes < dgx_knn_image_bytes(B, C, N)) return DGX_EINVAL;
     if ((reinterpret_cast<uintptr_t>(image) & 15) != 0) return DGX_EINVAL;
@@ -1324,7 +1329,7 @@ int dgx_knn_f32(const float* x, int64_t sB, int64_t sC, int64_t sN, int B, int C
                 int64_t* idx64, int32_t* idx32, void* workspace, size_t workspace_bytes, void* stream) {
     if (!x || B < 0 || C < 1 || N < 1 || k < 1 || k > N) return DGX_EINVAL;
     if (!idx64 && !idx32) return DGX_EINVAL;
-    if (C > 128 || k > 64 || N > FIX_MAXN) return DGX_EUNSUPPORTED;
+    if (!dgx_knn_fast_shape(C, k, N)) return DGX_EUNSUPPORTED;
     if (workspace_bytes < dgx_knn_workspace_bytes(B, C, N) || !workspace) return DGX_EINVAL;
     if (B == 0) return DGX_OK;
     float* xx = static_cast<float*>(workspace);

@@ -247,6 +247,8 @@ size_t dgx_knn_generic_workspace_bytes(int B, int C, int N) {
     return (xxf + (size_t)chunk_rows(N) * N) * sizeof(float);
 }
 
+int dgx_knn_generic_max_k(void) { return KG_MAXK; }
+
 int dgx_knn_generic_f32(const float* x, int64_t sB, int64_t sC, int64_t sN, int B, int C, int N, int k, int order,
                         int64_t* idx64, int32_t* idx32, float* vals, void* workspace, size_t workspace_bytes,
                         void* stream) {

@@ -27,6 +27,8 @@ _vp, _i64, _i32, _f32, _f64, _sz = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_in
 _SIGS = {
     "dgx_version": [],
     "dgx_strerror": [_i32],
+    "dgx_knn_fast_shape": [_i32, _i32, _i32],
+    "dgx_knn_generic_max_k": [],
     "dgx_knn_workspace_bytes": [_i32, _i32, _i32],
     "dgx_knn_image_bytes": [_i32, _i32, _i32],
     "dgx_knn_kernel_name": [_i32, _i32, _i32],

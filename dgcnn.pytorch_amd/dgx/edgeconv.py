@@ -27,7 +27,6 @@ The A/B switches below are the bits of the schedule's ``opts`` word
 (schedule.OPT_BITS; ``opts`` reads them when it is called, so a tool may set
 ``dgx.edgeconv.NAME`` at run time).
 """
-import ctypes
 import os
 import threading
 
@@ -85,26 +84,6 @@ def debug_capture():
 
 def set_debug_capture(d):
     _tls.debug = d
-
-
-def _reverse_graphs(idxs, B, N, k, dev):
-    """Reverse kNN graphs (CSR of in-edges) of all blocks in one launch
-    (dgx_graph_reverse_multi), on the current stream at the start of the
-    backward: the blocks' workgroups share the chip, and each cloud's index
-    list is re-scanned by fewer workgroups than per-block launches need. (A
-    build on a side stream overlapping the forward measured slower: 1.63 vs
-    1.56 ms/step at cfg2, the concurrent kernels contend for the L2 the kNN
-    operand images live in.)"""
-    M = B * N
-    n = len(idxs)
-    rowptrs = [torch.empty(M + 1, dtype=torch.int32, device=dev) for _ in range(n)]
-    edges = [torch.empty(M * k, dtype=torch.int32, device=dev) for _ in range(n)]
-    arr = ctypes.c_void_p * n
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().dgx_graph_reverse_multi(
-            n, arr(*[i.data_ptr() for i in idxs]), B, N, k, arr(*[r.data_ptr() for r in rowptrs]),
-            arr(*[e.data_ptr() for e in edges]), nat.stream_of(idxs[0])), "reverse graphs")
-    return list(zip(rowptrs, edges))
 
 
 def split_weight(w, cin, cout):

@@ -6,8 +6,9 @@ instead of one Python dispatch each.
 
 It is the same schedule the engine's autograd Functions (dgx.edgeconv,
 dgx.pointconv) and torch.library ops (dgx.library) call — all through the one
-binding, dgx.schedule — one C++ implementation for every configuration the
-reference's scripts run:
+binding, dgx.schedule, which also carries the kNN dispatch (dgx_host::knn: the
+chain's own kNN function, bound by dgx.ops.knn_raw) and the graph-feature ops —
+one C++ implementation for every configuration the reference's scripts run:
 precision bf16, fp32 or fp32_split (bf16 autocast -> bf16 GEMMs, fp16
 autocast -> split-bf16 fp32 GEMMs, dgx.precision.effective), BatchNorm in
 training or eval mode, momentum or cumulative running statistics, plain

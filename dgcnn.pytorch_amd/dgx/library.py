@@ -51,17 +51,6 @@ def _empty(dev, dtype=_F32):
     return torch.empty(0, dtype=dtype, device=dev)
 
 
-class _Rec:
-    """The autograd-context surface dgx.ops._GraphFeature uses, recorded so the
-    graph_feature ops can run its forward / backward body."""
-
-    def __init__(self):
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *t):
-        self.saved_tensors = t
-
-
 class _BNSpec:
     """The nn.BatchNorm fields dgx.bn reads, rebuilt from tensors that crossed
     the op boundary (the running statistics are read from the inputs and the
@@ -154,7 +143,7 @@ def graph_feature(x: Tensor, k: int, mode: int) -> tuple[Tensor, Tensor]:
     xf = x.float()
     idx = ops.knn_raw(xf.detach(), k, out_dtype=_I32)
     shared = idx._base is not None or getattr(ops._tls, "cache", None) is not None   # a cache entry: never alias it
-    return ops._GraphFeature.forward(_Rec(), xf, idx, mode), idx.clone() if shared else idx
+    return S.graph_feature(xf, idx, mode), idx.clone() if shared else idx
 
 
 @graph_feature.register_kernel("cpu")
@@ -174,12 +163,7 @@ def _(x, k, mode):
 
 @torch.library.custom_op("dgx::graph_feature_backward", mutates_args=(), device_types="cuda")
 def graph_feature_backward(grad: Tensor, idx: Tensor, C: int, mode: int) -> Tensor:
-    rec = _Rec()
-    rec.saved_tensors = (idx,)
-    rec.mode = mode
-    B, N, _ = idx.shape
-    rec.shape = (B, C, N)
-    return ops._GraphFeature.backward(rec, grad)[0]
+    return S.graph_feature_backward(grad, idx, C, mode)
 
 
 @graph_feature_backward.register_kernel("cpu")

@@ -1,8 +1,12 @@
 """Device ops behind the reference's graph functions (models/dgcnn.py:6-44).
 
 ``knn`` and ``graph_feature`` keep the reference's argument meaning, return
-shapes and dtypes; the work is done by libdgx.so on the tensor's own device
-and current stream.
+shapes and dtypes. Their launch schedule is the C++ one (libdgx_torch.so:
+dgx_host::knn, graph_feature, graph_feature_backward, reverse_graphs, called
+through dgx.schedule), on the tensor's own device and current stream; what
+lives here is what is Python's: the drop-in signatures, the reference's
+rounding-order rule (part of the kNN-sharing scope's key), that scope, and
+the autograd plumbing. Host tensors take dgx.cpu and load neither library.
 """
 import contextlib
 import threading
@@ -32,110 +36,47 @@ def _as_f32(x):
 
 
 def knn_image_buffers(B, C, N, dev):
-    """(xx, image) scratch of one kNN call (dgx_knn_prepare_f32's outputs); a
-    producer kernel may fill them (dgx_bn_lrelu_apply_knn_image_f32) and hand
-    them to knn_raw(prepared=...)."""
-    L = nat.lib()
-    img_bytes = L.dgx_knn_image_bytes(B, C, N)
-    xx = torch.empty((B * N,), dtype=torch.float32, device=dev)
-    img = torch.empty((max(img_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
-    return xx, img
-
-
-# shapes of the fused selection kernel (csrc/knn.hip); the rest take the
-# generic path (csrc/knn_generic.hip): same values, same canonical order
-FAST_MAXC, FAST_MAXK, FAST_MAXN = 128, 64, 12288
-GENERIC_MAXK = 8192
+    """(xx, image) scratch of one kNN call, for a producer kernel to fill and hand to knn_raw(prepared=...)."""
+    from . import schedule as S
+    return S.knn_image_buffers(B, C, N, dev)
 
 
 def fast_shape(C, k, N):
-    return C <= FAST_MAXC and k <= FAST_MAXK and N <= FAST_MAXN
+    """Whether the fused selection kernel is built for the shape (the rest take
+    the generic one): the kernels' own answer, a host query (no device needed)."""
+    return bool(nat.lib().dgx_knn_fast_shape(C, k, N))
 
 
-def _knn_generic(x, strides, shape, k, order, idx, vals, stream):
-    """dgx_knn_generic_f32 on a (B,C,N) view; a view with neither inner
-    stride 1 is read from a contiguous copy (the rounding order was taken from
-    the caller's strides)."""
-    B, C, N = shape
-    sB, sC, sN = strides
-    if k > GENERIC_MAXK:
-        raise NotImplementedError(f"dgx knn: k = {k} > {GENERIC_MAXK} neighbours")
-    if sN != 1 and sC != 1:
-        x = torch.as_strided(x, shape, strides).contiguous()
-        sB, sC, sN = x.stride()
-    L = nat.lib()
-    ws_bytes = L.dgx_knn_generic_workspace_bytes(B, C, N)
-    ws = torch.empty(((ws_bytes + 3) // 4,), dtype=torch.float32, device=x.device)
-    i64 = idx.dtype == torch.int64
-    with torch.cuda.device(x.device):
-        nat.check(L.dgx_knn_generic_f32(nat.f32(x), sB, sC, sN, B, C, N, k, order,
-                                        nat.ptr(idx, torch.int64) if i64 else None,
-                                        nat.i32(idx) if not i64 else None, nat.f32(vals), nat.f32(ws), ws_bytes,
-                                        stream), "knn (generic)")
-
-
-def knn_raw(x, k, order=None, out_dtype=torch.int64, strides=None, shape=None, return_values=False, prepared=None):
-    """kNN on a (B,C,N) fp32 view. ``strides``/``shape`` let callers describe a
-    strided slice of a larger buffer (the engine's point-major concat buffer).
-    ``prepared``: (xx, image) already holding |x|^2 in ``order`` and the operand
-    image of exactly this view (knn_image_buffers + a producer kernel): the
-    prepare pass is skipped."""
+def knn_raw(x, k, order=None, out_dtype=torch.int64, strides=None, shape=None, return_values=False, prepared=None,
+            generic=False):
+    """kNN on a (B,C,N) fp32 view, by the C++ schedule's dispatch
+    (dgx_host::knn: the fused kernel where it is built for the shape, else the
+    generic one). ``strides``/``shape`` let callers describe a strided slice of
+    a larger buffer (the engine's point-major concat buffer). ``prepared``:
+    (xx, image) already holding |x|^2 in ``order`` and the operand image of
+    exactly this view (knn_image_buffers + a producer kernel): the prepare pass
+    is skipped. ``generic``: the generic kernel on a shape the fused one takes
+    too. Inside a knn_cache scope a repeated call launches nothing."""
+    from . import schedule as S
     nat.require_device(x)
-    B, C, N = shape if shape is not None else x.shape
-    sB, sC, sN = strides if strides is not None else x.stride()
     if order is None:
         order = reduction_order(x)
-    if not (1 <= k <= N):
-        raise RuntimeError(f"knn: selected index k out of range (k={k}, N={N})")
-    generic = not fast_shape(C, k, N)
-    if generic and prepared is not None:
-        raise RuntimeError("knn: prepared operands exist for the fused kernel's shapes only")
+    if strides is not None or shape is not None:
+        x = torch.as_strided(x, shape if shape is not None else x.shape, strides if strides is not None else x.stride())
     cache = getattr(_tls, "cache", None)
     key = None
     if cache is not None and not return_values:
-        key = (x.device, x.data_ptr(), (B, C, N), (sB, sC, sN), x._version, k, order)
+        key = (x.device, x.data_ptr(), tuple(x.shape), x.stride(), x._version, k, order)
         hit = cache.get(key)
         if hit is not None:
             hit = hit[0]
             return hit if hit.dtype == out_dtype else hit.to(out_dtype)
-    L = nat.lib()
-    idx = torch.empty((B, N, k), dtype=out_dtype, device=x.device)
-    vals = torch.empty((B, N, k), dtype=torch.float32, device=x.device) if return_values else None
-    stream = nat.stream_of(x)
-    if generic:
-        _knn_generic(x, (sB, sC, sN), (B, C, N), k, order, idx, vals, stream)
-        if key is not None:
-            cache[key] = (idx, x)
-        return (idx, vals) if return_values else idx
-    img_bytes = L.dgx_knn_image_bytes(B, C, N)
-    if prepared is not None:
-        xx, img = prepared
-        if xx.numel() != B * N or img.numel() * 4 < img_bytes:
-            raise RuntimeError("knn: prepared |x|^2 / image buffers do not match the cloud")
-    else:
-        xx, img = knn_image_buffers(B, C, N, x.device)
-    with torch.cuda.device(x.device):
-        if prepared is None:
-            # |x|^2 and the MFMA operand image in one pass over x
-            nat.check(L.dgx_knn_prepare_f32(nat.f32(x), sB, sC, sN, B, C, N, order, nat.f32(xx), nat.f32(img),
-                                            img_bytes, stream), "knn prepare")
-        timing = getattr(_tls, "timing", None)
-        if timing is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = L.dgx_knn_select_f32(nat.f32(x), sB, sC, sN, nat.f32(xx), B, C, N, k,
-                                  nat.ptr(idx, torch.int64) if out_dtype == torch.int64 else None,
-                                  nat.i32(idx) if out_dtype == torch.int32 else None, nat.f32(vals),
-                                  nat.f32(img), img_bytes, stream)
-        if timing is not None:
-            ev1.record()
-            timing.append((ev0, ev1, 2.0 * B * N * N * C, (B, C, N, k)))
-    nat.check(rc, "knn")
+    r = S.knn(x.detach() if x.requires_grad else x, k, order, out_dtype, return_values, generic, prepared)
     if key is not None:
         # the entry holds x too: its storage (whose address is part of the key)
         # cannot be freed and reused by another tensor while the scope lives
-        cache[key] = (idx, x)
-    return (idx, vals) if return_values else idx
+        cache[key] = (r[0], x)
+    return tuple(r) if return_values else r[0]
 
 
 @contextlib.contextmanager
@@ -158,7 +99,7 @@ def knn_cache():
 
 
 class _Elapsed:
-    """An already-measured launch (C++ HIP events), shaped like the
+    """A measured launch (the C++ dispatch's HIP events), shaped like a
     (start_event, end_event) pair: start.elapsed_time(end) -> ms."""
 
     def __init__(self, ms):
@@ -170,17 +111,17 @@ class _Elapsed:
 
 def set_knn_timing(lst):
     """Optional per-thread instrumentation (tools, bench.py's roofline leg):
-    when a list, every kNN selection launch of this thread appends
-    (start_event, end_event, gram_flops, shape) recorded on the launch stream —
-    the Python dispatch's launches as they run, the C++ schedule's
-    (libdgx_torch.so) when the timing is switched off again (set_knn_timing(None))."""
+    while a list is set, the C++ dispatch (dgx_host::knn, the schedule's own
+    kNN calls included) puts HIP events around every fused-kernel selection
+    launch of this thread on its launch stream; switching the timing off again
+    (set_knn_timing(None)) appends (start_event, end_event, gram_flops,
+    (B, C, N, k)) per launch to that list, in launch order."""
+    from . import schedule as S
     prev = getattr(_tls, "timing", None)
-    from . import host
     if lst is not None:
-        host.load()
-        torch.ops.dgx_host.knn_timing(True)
+        S.knn_timing(True)
     elif prev is not None:
-        v = torch.ops.dgx_host.knn_timing(False)
+        v = S.knn_timing(False)
         for j in range(0, len(v), 6):
             prev.append((_Elapsed(v[j]), None, v[j + 1], (int(v[j + 2]), int(v[j + 3]), int(v[j + 4]), int(v[j + 5]))))
     _tls.timing = lst
@@ -199,46 +140,21 @@ def knn(x, k):
 
 
 class _GraphFeature(torch.autograd.Function):
+    """Autograd over dgx_host::graph_feature / graph_feature_backward."""
+
     @staticmethod
     def forward(ctx, x, idx32, mode):
-        x = x.float()
-        B, C, N = x.shape
-        k = idx32.shape[-1]
-        if mode in (nat.GF_CAT, nat.GF_DIFFCAT):
-            out = torch.empty((B, 2 * C, N, k), dtype=torch.float32, device=x.device)
-        elif mode == nat.GF_DISP:
-            out = torch.empty((B, C, N, k), dtype=torch.float32, device=x.device)
-        else:
-            out = torch.empty((B, N, k, C), dtype=torch.float32, device=x.device)
-        sB, sC, sN = x.stride()
-        with torch.cuda.device(x.device):
-            rc = nat.lib().dgx_graph_feature_f32(nat.f32(x), sB, sC, sN, B, C, N, nat.i32(idx32), k, mode,
-                                                 nat.f32(out), nat.stream_of(x))
-        nat.check(rc, "graph_feature")
+        from . import schedule as S
         ctx.save_for_backward(idx32)
         ctx.mode = mode
-        ctx.shape = (B, C, N)
-        return out
+        ctx.C = x.shape[1]
+        return S.graph_feature(x.float(), idx32, mode)
 
     @staticmethod
     def backward(ctx, dout):
+        from . import schedule as S
         (idx32,) = ctx.saved_tensors
-        B, C, N = ctx.shape
-        dout = dout.contiguous().float()
-        dx = torch.zeros((B, C, N), dtype=torch.float32, device=dout.device)
-        k = idx32.shape[-1]
-        with torch.cuda.device(dout.device):
-            if k <= 64 and B * N < (1 << 25):
-                # deterministic: pull over the reverse kNN graph (no float atomics)
-                from .edgeconv import _reverse_graphs
-                (rowptr, edges), = _reverse_graphs([idx32.contiguous()], B, N, k, dout.device)
-                rc = nat.lib().dgx_graph_feature_bwd_csr_f32(nat.f32(dout), B, C, N, k, ctx.mode, nat.i32(rowptr),
-                                                             nat.i32(edges), nat.f32(dx), nat.stream_of(dout))
-            else:
-                rc = nat.lib().dgx_graph_feature_bwd_f32(nat.f32(dout), B, C, N, nat.i32(idx32), k,
-                                                         ctx.mode, nat.f32(dx), nat.stream_of(dout))
-        nat.check(rc, "graph_feature backward")
-        return dx, None, None
+        return S.graph_feature_backward(dout, idx32, ctx.C, ctx.mode), None, None
 
 
 def graph_feature(x, k=20, knn_only=False, disp_only=False, idx=None, mode="cat"):

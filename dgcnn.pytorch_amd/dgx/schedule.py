@@ -2,12 +2,14 @@
 csrc/dgx_torch.cpp): every ``torch.ops.dgx_host`` call of the EdgeConv chain,
 conv5, PositionEmbedding's edge MLP and the one-op DGCNN goes through here, for
 the eager op (dgx.host), the autograd Functions (dgx.edgeconv, dgx.pointconv,
-dgx.edgemlp) and the torch.library ops (dgx.library) alike; dgx.gemm binds the
-schedule's GEMM and weight-prep helpers through ``host_ops``. What they share lives here once: the precision / options
-decision taken at forward entry, the BatchNorm argument lists, the kNN-sharing
-lookup, and the names of the saved-state lists the schedule hands back for
-backward (``dgx_host::layout()`` returns the C++ side's tables; a test holds
-the two equal).
+dgx.edgemlp) and the torch.library ops (dgx.library) alike, and so do the kNN
+dispatch, the reverse graphs and the graph feature that dgx.ops binds; dgx.gemm
+binds the schedule's GEMM and weight-prep helpers through ``host_ops``. What
+they share lives here once: the precision / options decision taken at forward
+entry, the BatchNorm argument lists, the kNN-sharing lookup, and the names of
+the saved-state lists the schedule hands back for backward
+(``dgx_host::layout()`` returns the C++ side's tables; a test holds the two
+equal).
 """
 from collections import namedtuple
 
@@ -110,6 +112,37 @@ def _host():
 
 # dgx.gemm's handle: its functions are the dgx_host::gemm_* / weight_prep* ops one to one, with nothing to share here
 host_ops = _host
+
+
+def knn(x, k, order, out_dtype, return_values, generic, prepared):
+    """-> [ids (B, N, k)] or [ids, values] of a (B, C, N) fp32 view; ``prepared``: (xx, image) or None."""
+    return _host().knn(x, k, order, out_dtype, return_values, generic, *(prepared or (None, None)))
+
+
+def knn_image_buffers(B, C, N, dev):
+    """-> (xx, image) scratch of one fused-kernel kNN call, for a producer kernel to fill."""
+    return _host().knn_image_buffers(B, C, N, torch.device(dev))
+
+
+def knn_timing(on):
+    """True: record this thread's kNN selection launches; False: stop, -> [ms, flops, B, C, N, k] per launch."""
+    return _host().knn_timing(on)
+
+
+def reverse_graphs(idxs):
+    """-> [(rowptr, edges)] per contiguous int32 (B, N, k) graph: the CSR lists of its in-edges."""
+    r = _host().reverse_graphs(idxs)
+    return list(zip(r[:len(idxs)], r[len(idxs):]))
+
+
+def graph_feature(x, idx, mode):
+    """-> the edge tensor of an fp32 (B, C, N) cloud over its int32 kNN graph, in the layout of ``mode`` (nat.GF_*)."""
+    return _host().graph_feature(x, idx, mode)
+
+
+def graph_feature_backward(dout, idx, C, mode):
+    """-> dx (B, C, N)"""
+    return _host().graph_feature_backward(dout, idx, C, mode)
 
 
 def chain_forward(x, k, weights, gammas, betas, bn, d, need_grad, prep, idx0):

@@ -51,12 +51,16 @@ const char* dgx_strerror(int code);
  * `order` for |x|^2), sorted by pd descending, ties by index ascending.
  * Outputs local indices 0..N-1 into idx64 (B,N,k) int64 and/or idx32 (either
  * may be NULL). Workspace: dgx_knn_workspace_bytes(B,C,N), 16-byte aligned.
- * Supports C <= 128, 1 <= k <= min(N, 64). */
+ * Supports the shapes of dgx_knn_fast_shape, 1 <= k <= N. */
 size_t dgx_knn_workspace_bytes(int B, int C, int N);
 int dgx_knn_f32(const float* x, int64_t sB, int64_t sC, int64_t sN,
                 int B, int C, int N, int k, int order,
                 int64_t* idx64, int32_t* idx32,
                 void* workspace, size_t workspace_bytes, void* stream);
+/* Host-side: 1 where the fused kernel above is built for (C, k, N) — C <= 128,
+ * k <= 64, N <= 12288 — else 0 (dgx_knn_generic_f32 takes those). The one
+ * statement of these limits: every caller's routing asks here. */
+int dgx_knn_fast_shape(int C, int k, int N);
 
 /* The stages of dgx_knn_f32, separately. dgx_sqnorm_f32: |x_i|^2 in the
  * reference's rounding order into xx (B*N fp32, dgcnn.py:8).
@@ -101,8 +105,10 @@ int dgx_knn_select_f32(const float* x, int64_t sB, int64_t sC, int64_t sN,
  * k <= N and N): |x|^2 in the reference's order for any C, the Gram chain on
  * dgx_gemm_f32 (one fp32 MFMA accumulation chain per output, c in order), and
  * an exact radix select + bitonic sort per query row — identical values and
- * canonical order. x needs sN == 1 or sC == 1; k <= 8192. Workspace:
- * dgx_knn_generic_workspace_bytes(B,C,N) (|x|^2 + one chunk of dot rows). */
+ * canonical order. x needs sN == 1 or sC == 1; k <= dgx_knn_generic_max_k()
+ * (8192). Workspace: dgx_knn_generic_workspace_bytes(B,C,N) (|x|^2 + one chunk
+ * of dot rows). */
+int dgx_knn_generic_max_k(void);
 size_t dgx_knn_generic_workspace_bytes(int B, int C, int N);
 int dgx_knn_generic_f32(const float* x, int64_t sB, int64_t sC, int64_t sN,
                         int B, int C, int N, int k, int order,

@@ -11,6 +11,7 @@ import torch
 from dgx import _native as nat
 from dgx import bn as bn_
 from dgx import edgeconv as E
+from dgx import schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +47,7 @@ def test_backward_scatter_finalize(cuda, B, N, k, Co, ev, packed):
         nat.check(L.dgx_edge_bwd_dz_packed_f32(nat.f32(dY), Co, nat.f32(ysel), nat.u8(arg), *bn_args), "dz")
     else:
         nat.check(L.dgx_edge_bwd_dz_f32(nat.f32(dY), Co, nat.f32(ysel), *bn_args), "dz")
-    (rowptr, edges), = E._reverse_graphs([idx], B, N, k, cuda)
+    (rowptr, edges), = schedule.reverse_graphs([idx])
     dgamma, dbeta, c0, c1 = bn_.backward_consts(partials, nblk, float(M * k), st, stream)
     ref = torch.empty(M, 2 * Co, device=cuda)
     common = (B, N, k, Co, nat.f32(st.scale), nat.f32(c0), nat.f32(c1), nat.f32(ref), 0, stream)

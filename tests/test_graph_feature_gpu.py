@@ -86,3 +86,35 @@ def test_graph_feature_rejects_out_of_range_ids(cuda):
     with pytest.raises(RuntimeError, match="does not match"):
         ops.graph_feature(x, k=k, idx=idx[:, :32])
     assert ops.graph_feature(x, k=k, idx=idx).shape == (B, 2 * C, N, k)
+
+
+@pytest.mark.parametrize("mode", ["cat", "disp", "knn", "diff"])
+def test_graph_feature_backward_atomic_route_exact(cuda, mode):
+    """k = 65 > 64: the backward takes the float-atomic route
+    (dgx_graph_feature_bwd_f32) through dgx_host::graph_feature_backward. With
+    small-integer features and upstream gradients every fp32 sum is exact in
+    any order, so the gradient equals the reference's autograd bit for bit."""
+    from dgx import ops
+    from models.dgcnn import knn
+    B, C, N, k = 1, 3, 70, 65
+    g = torch.Generator().manual_seed(11)
+    x = torch.randint(-4, 5, (B, C, N), generator=g).float()
+    idx = knn(x.to(cuda), k).cpu()
+
+    def ref_feature(xc):
+        if mode == "diff":   # (x_j - x_i, x_i): the reference's displacement and its centre half
+            return torch.cat((R.graph_feature(xc, k, idx=idx, disp_only=True),
+                              R.graph_feature(xc, k, idx=idx)[:, C:]), 1)
+        return R.graph_feature(xc, k, idx=idx, knn_only=mode == "knn", disp_only=mode == "disp")
+    xc = x.clone().requires_grad_(True)
+    ref = ref_feature(xc)
+    gout = torch.randint(-3, 4, ref.shape, generator=g).float()
+    # every partial sum of the gradient is an integer below 2^24: exact in fp32, in any order
+    assert float(gout.abs().sum()) < 2 ** 24 and float(x.abs().max()) * 2 < 2 ** 24
+    ref.backward(gout)
+    xg = x.to(cuda).requires_grad_(True)
+    out = ops.graph_feature(xg, k=k, knn_only=mode == "knn", disp_only=mode == "disp", idx=idx.to(cuda),
+                            mode="diff" if mode == "diff" else "cat")
+    out.backward(gout.to(cuda))
+    np.testing.assert_array_equal(out.detach().cpu().numpy(), ref.detach().numpy())
+    np.testing.assert_array_equal(xg.grad.cpu().numpy(), xc.grad.numpy())

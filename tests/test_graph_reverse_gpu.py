@@ -69,3 +69,20 @@ def test_reverse_graph_bench_size_from_knn(cuda):
     ref_rp, ref_ed = _reference(idx)
     np.testing.assert_array_equal(rp, ref_rp)
     np.testing.assert_array_equal(ed, ref_ed)
+
+
+@pytest.mark.parametrize("B,N,k", [(2, 100, 7), (1, 5, 1)])
+@pytest.mark.parametrize("n", [1, 2, 8, 9])
+def test_reverse_graphs_multi(cuda, n, B, N, k):
+    """schedule.reverse_graphs (dgx_graph_reverse_multi, what the chain's and
+    the graph feature's backward build their graphs with): n distinct graphs,
+    each equal to numpy's; n = 9 takes a second launch (8 graphs per launch)."""
+    from dgx import schedule
+    idxs = [_random_graph(B, N, k, 77 * n + 1000 * j + N) for j in range(n)]
+    assert len({i.tobytes() for i in idxs}) == n
+    got = schedule.reverse_graphs([torch.from_numpy(i).to(cuda) for i in idxs])
+    assert len(got) == n
+    for idx, (rowptr, edges) in zip(idxs, got):
+        ref_rp, ref_ed = _reference(idx)
+        np.testing.assert_array_equal(rowptr.cpu().numpy(), ref_rp)
+        np.testing.assert_array_equal(edges.cpu().numpy(), ref_ed)

@@ -45,7 +45,7 @@ def test_generic_knn_large_cloud(cuda):
 
 
 def test_generic_knn_large_k(cuda):
-    """k in the generic kernel's largest class (4096 < k <= 8192, GENERIC_MAXK):
+    """k in the generic kernel's largest class (4096 < k <= 8192 = dgx_knn_generic_max_k()):
     the 8192-wide bitonic stage and its LDS buffer run on the device."""
     _check(_cloud(1, 3, 6000, seed=21), 5000)
 
@@ -65,13 +65,9 @@ def test_generic_equals_fused_kernel(cuda):
     from dgx import ops
     for layout in ("bcn", "perm"):
         x = _cloud(2, 64, 1024, seed=9, layout=layout).to("cuda")
-        B, C, N = x.shape
         k = 20
         idx_f, val_f = ops.knn_raw(x, k, return_values=True)
-        idx_g = torch.empty_like(idx_f)
-        val_g = torch.empty_like(val_f)
-        ops._knn_generic(x, x.stride(), (B, C, N), k, ops.reduction_order(x), idx_g, val_g,
-                         ops.nat.stream_of(x))
+        idx_g, val_g = ops.knn_raw(x, k, return_values=True, generic=True)
         assert torch.equal(idx_f, idx_g) and torch.equal(val_f, val_g), layout
 
 

@@ -226,3 +226,63 @@ def test_apply_writes_next_knn_image(cuda, B, N, Co):
     a = knn_raw(xcat[:, off:], 20, prepared=(xx, img), **kw)
     b = knn_raw(xcat[:, off:], 20, **kw)
     assert torch.equal(a, b)
+
+
+def test_knn_timing_contract(cuda):
+    """set_knn_timing: after switching off, the list holds one (t0, t1,
+    gram_flops, (B, C, N, k)) per fused-kernel selection launch of this thread,
+    in launch order, t0.elapsed_time(t1) in ms (what bench.py's roofline leg
+    reads). A knn_cache hit launches nothing and the generic kernel is not
+    timed, so neither adds a record; nor does a call after switching off."""
+    import math
+    from dgx import ops
+
+    def cloud(B, N, seed):
+        return torch.from_numpy(synth.cube_clouds(B, N, seed)).to(cuda).permute(0, 2, 1).contiguous()
+    B, C, N, k = 2, 3, 64, 4
+    x, big = cloud(B, N, 5), cloud(1, 128, 6)
+    assert ops.fast_shape(C, k, N) and not ops.fast_shape(3, 65, 128)
+    lst = []
+    ops.set_knn_timing(lst)
+    try:
+        with ops.knn_cache():
+            first = ops.knn_raw(x, k)
+            hit = ops.knn_raw(x, k)      # the scope's repeat: no launch
+        generic = ops.knn_raw(big, 65)   # the generic kernel: not timed
+    finally:
+        ops.set_knn_timing(None)
+    assert hit is first and tuple(generic.shape) == (1, 128, 65)
+    assert len(lst) == 1
+    t0, t1, flops, shape = lst[0]
+    assert shape == (B, C, N, k) and flops == 2.0 * B * N * N * C
+    ms = t0.elapsed_time(t1)
+    assert math.isfinite(ms) and ms > 0
+    ops.knn_raw(x, k)                    # timing is off: nothing is added
+    assert len(lst) == 1
+    # records come back in launch order
+    wide = torch.randn(B, 9, N, device=cuda)
+    lst = []
+    ops.set_knn_timing(lst)
+    try:
+        ops.knn_raw(wide, k)
+        ops.knn_raw(x, k)
+        ops.knn_raw(wide, k)
+    finally:
+        ops.set_knn_timing(None)
+    assert [r[3] for r in lst] == [(B, 9, N, k), (B, 3, N, k), (B, 9, N, k)]
+
+
+def test_knn_limit_error_before_allocation(cuda):
+    """k above the generic kernel's limit (dgx_knn_generic_max_k() = 8192)
+    raises NotImplementedError, and the check runs before anything is
+    allocated: the allocator's byte count is unchanged across the call, and so
+    is its peak (an allocation freed again by the exception would raise it)."""
+    from dgx import ops
+    x = torch.from_numpy(synth.cube_clouds(1, 8200, 7)).to(cuda).permute(0, 2, 1).contiguous()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    with pytest.raises(NotImplementedError, match="k = 8193 > 8192 neighbours"):
+        ops.knn_raw(x, 8193)
+    assert torch.cuda.memory_allocated() == before
+    assert torch.cuda.max_memory_allocated() == before

@@ -87,7 +87,14 @@ def test_host_op_library_loads():
         "pointconv_backward": "dgx_host::pointconv_backward(Tensor dout, Tensor[] saved",
         "edge_mlp2_forward": "dgx_host::edge_mlp2_forward(Tensor x, Tensor idx, int k, Tensor w1",
         "edge_mlp2_backward": "dgx_host::edge_mlp2_backward(Tensor dout, Tensor[] saved, Tensor w1, Tensor w2",
+        "knn": "dgx_host::knn(Tensor x, int k, int order, ScalarType ids, bool values, bool generic, Tensor? xx, "
+               "Tensor? image) -> Tensor[]",
+        "knn_image_buffers": "dgx_host::knn_image_buffers(int B, int C, int N, Device device) -> (Tensor, Tensor)",
         "knn_timing": "dgx_host::knn_timing(bool on) -> float[]",
+        "reverse_graphs": "dgx_host::reverse_graphs(Tensor[] idxs) -> Tensor[]",
+        "graph_feature": "dgx_host::graph_feature(Tensor x, Tensor idx, int mode) -> Tensor",
+        "graph_feature_backward": "dgx_host::graph_feature_backward(Tensor dout, Tensor idx, int C, int mode) "
+                                  "-> Tensor",
         "gemm_xwt": "dgx_host::gemm_xwt(Tensor x, Tensor w, Tensor(a!)? out, bool stats, bool out_bf16",
         "gemm_xw": "dgx_host::gemm_xw(Tensor x, Tensor w, Tensor(a!)? out, bool accumulate)",
         "gemm_atb": "dgx_host::gemm_atb(Tensor a, Tensor b, Tensor(c!) out, int split_rows, bool lds, int slab_cap_mb)",
@@ -178,3 +185,17 @@ def test_knn_shape_routing():
     L = _native.lib()
     # |x|^2 (B*N, 16-byte rounded) + one chunk of dot rows (min(N, 2^24 / N rounded to 64) x N)
     assert L.dgx_knn_generic_workspace_bytes(2, 256, 1000) == (2000 + 1000 * 1000) * 4
+
+
+def test_knn_limits_exported():
+    """The kernels state their own shape limits (host queries of libdgx.so: no
+    device needed): the fused kernel's C <= 128, k <= 64, N <= 12288, which
+    ``ops.fast_shape`` and the C++ dispatch both ask for, and the generic
+    kernel's k <= 8192."""
+    from dgx import _native, ops
+    L = _native.lib()
+    assert L.dgx_knn_fast_shape(128, 64, 12288) == 1 and L.dgx_knn_fast_shape(129, 20, 1024) == 0
+    assert L.dgx_knn_fast_shape(3, 65, 1024) == 0 and L.dgx_knn_fast_shape(3, 20, 12289) == 0
+    for shape in ((1, 1, 1), (3, 20, 2048), (128, 64, 12288), (129, 64, 12288), (128, 65, 12288), (128, 64, 12289)):
+        assert ops.fast_shape(*shape) is bool(L.dgx_knn_fast_shape(*shape)), shape
+    assert L.dgx_knn_generic_max_k() == 8192

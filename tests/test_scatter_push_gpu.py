@@ -21,6 +21,7 @@ import torch
 from dgx import _native as nat
 from dgx import bn as bn_
 from dgx import edgeconv as E
+from dgx import schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +55,7 @@ def _setup(cuda, B, N, k, Co, hubs=False, seed=0, packed=False):
         nat.check(L.dgx_edge_bwd_dz_packed_f32(nat.f32(dY), Co, nat.f32(ysel), nat.u8(arg), *bn_args), "dz")
     else:
         nat.check(L.dgx_edge_bwd_dz_f32(nat.f32(dY), Co, nat.f32(ysel), *bn_args), "dz")
-    (rowptr, edges), = E._reverse_graphs([idx], B, N, k, cuda)
+    (rowptr, edges), = schedule.reverse_graphs([idx])
     c = bn_.backward_consts(partials, nblk, float(M * k), st, stream)
     return dict(L=L, B=B, N=N, k=k, Co=Co, M=M, PQ=PQ, idx=idx, arg=arg, sumP=sumP, st=st, dz=dz, partials=partials,
                 nblk=nblk, rowptr=rowptr, edges=edges, c0=c[2], c1=c[3], stream=stream)
