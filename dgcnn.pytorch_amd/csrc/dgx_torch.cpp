@@ -30,6 +30,7 @@
 //   knn_timing                            per-thread HIP-event timing of the kNN selection launches
 //   reverse_graphs                        CSR in-edge lists of kNN graphs, 8 graphs per launch
 //   graph_feature / graph_feature_backward get_graph_feature's edge tensor after the kNN, and its gradient
+//   vattn_forward                          the fused kNN vector attention (attention.py:115-150)
 //   layout                                the name tables of the saved-state lists and the opts word
 //                                         (dgx.schedule names the same fields: one layout, checked by a test)
 #include <ATen/ATen.h>
@@ -2118,6 +2119,38 @@ Tensor graph_feature_backward(Tensor dout, const Tensor& idx, int64_t C, int64_t
   return dx;
 }
 
+// dgx_host::vattn_forward -> agg (B*N, Dm): the fused kNN vector attention (attention.py:115-150, csrc/vattn.hip).
+// weights: pos_mlp's and attn_mlp's (w1, b1, w2, b2), nn.Linear layout
+Tensor vattn_forward(const Tensor& D, const Tensor& V, const Tensor& pos, const Tensor& idx, int64_t gather_stride,
+                     at::TensorList weights, bool bf16) {
+  check_ids(idx);
+  const int64_t B = idx.size(0), N = idx.size(1), k = idx.size(2);
+  auto dense = [&](const Tensor& t) {
+    return t.is_cuda() && t.device() == idx.device() && t.scalar_type() == at::kFloat && t.is_contiguous();
+  };
+  TORCH_CHECK(dense(D) && dense(V) && D.dim() == 2 && D.sizes() == V.sizes(),
+              "vattn: D and V are contiguous fp32 (rows, Dm) tables on the ids' device");
+  TORCH_CHECK(dense(pos) && pos.dim() == 2 && pos.size(0) == B * N && pos.size(1) == 3,
+              "vattn: pos is a contiguous fp32 (B*N, 3) table");
+  TORCH_CHECK(weights.size() == 8, "vattn: pos_mlp and attn_mlp weights (w1, b1, w2, b2 each) expected");
+  for (const auto& w : weights) TORCH_CHECK(dense(w), "vattn: weights are contiguous fp32 on the ids' device");
+  const int64_t Dm = D.size(1), Hp = weights[0].size(0), H = weights[4].size(0);
+  const std::vector<int64_t> want[8] = {{Hp, 3}, {Hp}, {Dm, Hp}, {Dm}, {H, Dm}, {H}, {Dm, H}, {Dm}};
+  for (int j = 0; j < 8; ++j) TORCH_CHECK(weights[j].sizes() == want[j], "vattn: weight ", j, " has the wrong shape");
+  TORCH_CHECK(gather_stride >= 0 && (B == 0 || (B - 1) * gather_stride + N <= D.size(0)),
+              "vattn: gathered rows leave the tables");
+  TORCH_CHECK(B * N < ((int64_t)1 << 31) && dgx_vattn_fused_shape((int)Dm, (int)H, (int)Hp, (int)k),
+              "vattn: no fused kernel for Dm ", Dm, ", H ", H, ", Hp ", Hp, ", k ", k);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(idx.device());
+  Dev d(idx);
+  Tensor agg = at::empty({B * N, Dm}, d.f32);
+  check(dgx_vattn_fwd(P(D), P(V), D.size(0), P(pos), P<int32_t>(idx), (int)B, (int)N, (int)k, gather_stride,
+                      P(weights[0]), P(weights[1]), P(weights[2]), P(weights[3]), P(weights[4]), P(weights[5]),
+                      P(weights[6]), P(weights[7]), (int)Dm, (int)H, (int)Hp, bf16 ? 1 : 0, P(agg), d.stream),
+        "vattn forward");
+  return agg;
+}
+
 // dgx_host::knn_timing(on): on = true clears and starts recording this thread's kNN
 // selection launches; on = false stops and returns [ms, flops, B, C, N, k] per launch
 std::vector<double> knn_timing(bool on) {
@@ -2176,6 +2209,8 @@ TORCH_LIBRARY(dgx_host, m) {
   m.def("reverse_graphs(Tensor[] idxs) -> Tensor[]");
   m.def("graph_feature(Tensor x, Tensor idx, int mode) -> Tensor");
   m.def("graph_feature_backward(Tensor dout, Tensor idx, int C, int mode) -> Tensor");
+  m.def("vattn_forward(Tensor D, Tensor V, Tensor pos, Tensor idx, int gather_stride, Tensor[] weights, bool bf16) "
+        "-> Tensor");
   m.def("edge_mlp2_forward(Tensor x, Tensor idx, int k, Tensor w1, Tensor g1, Tensor b1, Tensor w2, Tensor g2, "
         "Tensor b2, Tensor?[] bn_t, float[] bn_f, int[] bn_i, str[] groups, bool bf16, bool need_grad, "
         "bool fused_bwd) -> (Tensor, Tensor[])");
@@ -2224,4 +2259,5 @@ TORCH_LIBRARY_IMPL(dgx_host, CompositeExplicitAutograd, m) {
   m.impl("reverse_graphs", reverse_graphs_op);
   m.impl("graph_feature", graph_feature);
   m.impl("graph_feature_backward", graph_feature_backward);
+  m.impl("vattn_forward", vattn_forward);
 }

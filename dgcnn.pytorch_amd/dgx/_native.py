@@ -139,6 +139,9 @@ _SIGS = {
     "dgx_gemm_dz2_bf16": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
     "dgx_edge_mlp_fused_fwd_bf16": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp,
                                     _vp, _i32, _vp, _vp],
+    "dgx_vattn_fused_shape": [_i32, _i32, _i32, _i32],
+    "dgx_vattn_fwd_points": [],
+    "dgx_vattn_fwd": [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64] + [_vp] * 8 + [_i32, _i32, _i32, _i32, _vp, _vp],
     "dgx_smoothed_ce_workspace_bytes": [_i64],
     "dgx_smoothed_ce_fwd": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp,
                             _sz, _vp],

@@ -132,6 +132,47 @@ def edge_mlp2(x, k, conv1, conv2, training=None, knn_src=None):
     return conv2(h1).max(dim=-1, keepdim=False)[0].contiguous()
 
 
+def vattn_params(pos_mlp, attn_mlp):
+    """(w1, b1, w2, b2) of pos_mlp then of attn_mlp: Linear-ReLU-Linear Sequentials
+    (reference attention.py:93-105), or already a sequence of those four tensors."""
+    out = []
+    for m in (pos_mlp, attn_mlp):
+        out += [m[0].weight, m[0].bias, m[2].weight, m[2].bias] if isinstance(m, torch.nn.Module) else list(m)
+    return out
+
+
+def vattn_edges(Dj, Vj, delta, params):
+    """The per-edge body of VectorAttention.forward (reference attention.py:121-150)
+    on gathered rows Dj = (q - k)[idx], Vj = v[idx] (P, k, Dm) and delta (P, k, 3),
+    in the reference's op order -> agg (P, Dm). Any dtype and device."""
+    pw1, pb1, pw2, pb2, aw1, ab1, aw2, ab2 = params
+    r = F.linear(F.relu(F.linear(delta, pw1, pb1)), pw2, pb2)          # attention.py:121
+    sim = F.linear(F.relu(F.linear(Dj + r, aw1, ab1)), aw2, ab2)       # :141
+    attn = F.normalize(sim.softmax(dim=-1), dim=-2)                     # :145-146
+    return torch.einsum('ijd,ijd->id', attn, Vj + r).contiguous()      # :137, :150
+
+
+def vattn_rows(idx, gather_stride):
+    """(B*N, k) int64 rows of the gather tables: b * gather_stride + id."""
+    B, N, k = idx.shape
+    off = torch.arange(B, device=idx.device).view(B, 1, 1) * int(gather_stride)
+    return (idx.long() + off).view(B * N, k)
+
+
+def vector_attention(D, V, pos, idx, pos_mlp, attn_mlp, gather_stride=0):
+    """The composed kNN vector attention (reference attention.py:115-150): D =
+    w_q(query) - w_k(key) and V = w_v(value) as (rows, Dm) tables, pos (B*N, 3),
+    idx (B, N, k) local ids; the gathered row of cloud b is b * gather_stride + id
+    (0: the reference's gather of cloud 0's rows) -> agg (B*N, Dm). Generic in
+    dtype and device, differentiable by torch autograd in everything but idx."""
+    B, N, k = idx.shape
+    rows = vattn_rows(idx, gather_stride).view(-1)
+    Dj = D[rows].view(B * N, k, -1)
+    Vj = V[rows].view(B * N, k, -1)
+    delta = pos[rows].view(B * N, k, 3) - pos.view(B * N, 1, 3)
+    return vattn_edges(Dj, Vj, delta, vattn_params(pos_mlp, attn_mlp))
+
+
 def hog_1x1(x, idx):
     """compute_hog_1x1 after its kNN call (reference model_partseg.py:28-92) on
     the host, as the reference runs it: LAPACK SVD (numpy) of every point's

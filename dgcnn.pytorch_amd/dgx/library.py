@@ -17,6 +17,8 @@ tracing, autocast rules and autograd formulas, so ``torch.compile`` /
   dgx::pointconv(X, X16, B, N, conv/BN tensors, ...) -> (out, updated
       running statistics, saved state)                   dgcnn.py:100-102
       (+ dgx::pointconv_backward)
+  dgx::vattn(D, V, pos, idx, gather_stride, 8 weights, bf16) -> agg
+      (+ dgx::vattn_backward)                            attention.py:115-150
 
 The ops are functional: BatchNorm running statistics come back as outputs (the
 finalize kernels read the module buffers and write the new values straight
@@ -691,3 +693,49 @@ def _(x, idx):
 def _(x, idx):
     B, _, N = x.shape
     return x.new_empty((B, N, 18), dtype=_F32)
+
+
+# ------------------------------------------------------- vector attention ----
+# dgx::vattn: the fused kNN vector attention (reference models/attention.py:
+# 115-150; dgx.vattn). The backward op is dgx.vattn's chunked recompute; the
+# precision of the forward's entry is an explicit argument (the backward is the
+# same in both modes).
+@torch.library.custom_op("dgx::vattn", mutates_args=(), device_types="cuda")
+def vattn(D: Tensor, V: Tensor, pos: Tensor, idx: Tensor, gather_stride: int, pw1: Tensor, pb1: Tensor, pw2: Tensor,
+          pb2: Tensor, aw1: Tensor, ab1: Tensor, aw2: Tensor, ab2: Tensor, bf16: bool) -> Tensor:
+    weights = [w.detach().float().contiguous() for w in (pw1, pb1, pw2, pb2, aw1, ab1, aw2, ab2)]
+    return S.vattn_forward(D, V, pos, idx, gather_stride, weights, S.Decision(bf16, 0))
+
+
+@vattn.register_fake
+def _(D, V, pos, idx, gather_stride, pw1, pb1, pw2, pb2, aw1, ab1, aw2, ab2, bf16):
+    return D.new_empty((idx.shape[0] * idx.shape[1], D.shape[1]), dtype=_F32)
+
+
+@torch.library.custom_op("dgx::vattn_backward", mutates_args=(), device_types="cuda")
+def vattn_backward(g: Tensor, D: Tensor, V: Tensor, pos: Tensor, idx: Tensor, gather_stride: int, pw1: Tensor,
+                   pb1: Tensor, pw2: Tensor, pb2: Tensor, aw1: Tensor, ab1: Tensor, aw2: Tensor,
+                   ab2: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from . import vattn as VA
+    dD, dV, dp = VA.backward(g, D, V, pos, idx, gather_stride, [pw1, pb1, pw2, pb2, aw1, ab1, aw2, ab2])
+    return (dD, dV, *dp)
+
+
+@vattn_backward.register_fake
+def _(g, D, V, pos, idx, gather_stride, pw1, pb1, pw2, pb2, aw1, ab1, aw2, ab2):
+    return (torch.empty_like(D, dtype=_F32), torch.empty_like(V, dtype=_F32),
+            *(torch.empty_like(w, dtype=_F32) for w in (pw1, pb1, pw2, pb2, aw1, ab1, aw2, ab2)))
+
+
+def _vattn_setup(ctx, inputs, output):
+    ctx.gather_stride = inputs[4]
+    ctx.save_for_backward(*inputs[:4], *inputs[5:13])
+
+
+def _vattn_bwd(ctx, g):
+    D, V, pos, idx, *params = ctx.saved_tensors
+    r = torch.ops.dgx.vattn_backward(g.contiguous(), D, V, pos, idx, ctx.gather_stride, *params)
+    return (r[0], r[1], None, None, None, *r[2:], None)
+
+
+torch.library.register_autograd("dgx::vattn", _vattn_bwd, setup_context=_vattn_setup)

@@ -145,6 +145,12 @@ def graph_feature_backward(dout, idx, C, mode):
     return _host().graph_feature_backward(dout, idx, C, mode)
 
 
+def vattn_forward(D, V, pos, idx, gather_stride, weights, d):
+    """-> agg (B*N, Dm) of the fused kNN vector attention; ``weights``: pos_mlp's and attn_mlp's (w1, b1, w2, b2),
+    ``d``: decide() — bf16 runs the bf16 kernel, fp32 and fp32_split the fp32 one (never narrower than asked)."""
+    return _host().vattn_forward(D, V, pos, idx, int(gather_stride), list(weights), bool(d.bf16))
+
+
 def chain_forward(x, k, weights, gammas, betas, bn, d, need_grad, prep, idx0):
     """-> (xcat, xcat16, saved, prep); ``bn``: bn_lists of the blocks, ``d``: decide()."""
     return _host().chain_forward(x, k, weights, gammas, betas, bn.t, bn.f, bn.i, bn.groups, bn.slopes, d.bf16,

@@ -565,6 +565,30 @@ int dgx_edge_mlp_scatter_f32(const void* g, int g_bf16, const float* PQ, int ldp
                              const int32_t* rowptr, const int32_t* edges, int B, int N, int k, int C1,
                              const float* scale, const float* c0, const float* c1, float* dPQ, void* stream);
 
+/* ---- v1: kNN vector attention, replaces models/attention.py:115-150
+ * (VectorAttention.forward between its q/k/v projections and to_out) in one
+ * kernel that writes only agg (B*N x Dm fp32). D = w_q(query) - w_k(key) and
+ * V = w_v(value) are the gather tables (rows x Dm fp32), pos the (B*N x 3)
+ * positions, idx (B, N, k) int32 LOCAL ids in [0, N). The gathered row of
+ * cloud b is b * gather_stride + id in D, V and pos alike: 0 is the reference
+ * (every cloud gathers cloud 0's rows, attention.py:116-134 index the
+ * (B*N, C) views with ids that carry no batch offset), N gathers each cloud's
+ * own rows; (B - 1) * gather_stride + N <= rows. The centre row is b*N + i.
+ *   r = pos_w2 relu(pos_w1 (pos_j - pos_i) + pos_b1) + pos_b2   (3 -> Hp -> Dm)
+ *   s = attn_w2 relu(attn_w1 (D_j + r) + attn_b1) + attn_b2     (Dm -> H -> Dm)
+ *   a = softmax(s over Dm);  agg = sum_j a (V_j + r) / max(|a|_2 over j, 1e-12)
+ * Weights are nn.Linear's (out x in) fp32, 16-byte aligned. bf16 != 0: the
+ * three MFMA GEMMs take bf16-rounded operands (fp32 accumulation), else exact
+ * fp32 products; everything else is fp32 in both. Built for the shapes of
+ * dgx_vattn_fused_shape (Dm 64, H 256, Hp 64, 1 <= k <= 64); others return
+ * DGX_EUNSUPPORTED. dgx_vattn_fwd_points: points per workgroup. */
+int dgx_vattn_fused_shape(int Dm, int H, int Hp, int k);
+int dgx_vattn_fwd_points(void);
+int dgx_vattn_fwd(const float* D, const float* V, int64_t rows, const float* pos, const int32_t* idx, int B, int N,
+                  int k, int64_t gather_stride, const float* pos_w1, const float* pos_b1, const float* pos_w2,
+                  const float* pos_b2, const float* attn_w1, const float* attn_b1, const float* attn_w2,
+                  const float* attn_b2, int Dm, int H, int Hp, int bf16, float* agg, void* stream);
+
 /* ---- f1: compute_hog_1x1 on the device, replaces models/model_partseg.py:26-92
  * after the kNN call (the D2H copy, np.linalg.svd on B*N k x 3 matrices, the H2D
  * copy and the histogram votes). x: contiguous (B, 3, N) fp32; idx: (B, N, k)
