@@ -1133,15 +1133,45 @@ int launch_gemm256(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, int M
     return hipGetLastError() == hipSuccess ? DGX_OK : DGX_ELAUNCH;
 }
 
+// ---- tile choice of the LDS-DMA path: host arithmetic shared by the launchers
+// (launch_gemm_lds, dgx_gemm_lds_bf16) and the dgx_gemm_lds_tile query ----
+// large NT GEMMs (conv5 forward and input gradient): 256 x 256 tiles when
+// they fill the chip (>= 256 tiles) and every tile is whole along N and K
+inline bool lds_big(int M, int N, int K, int a_k) {
+    return (int64_t)((M + G3_BM - 1) / G3_BM) * ((N + G3_BN - 1) / G3_BN) >= 256 && N % G3_BN == 0 &&
+           K % G3_BK == 0 && a_k % G3_BK == 0;
+}
+inline int lds_bn(int N) { return N > 64 ? 128 : 64; }
+// skinny outputs (few 128-row tiles): 64-row tiles double the workgroups so
+// two share each CU and hide each other's load latency; the statistics
+// epilogues keep 128 rows (one partial row per 128-row block)
+inline int lds_bm(int M, int N, int bn, int slabs, int epi) {
+    const bool can_half = epi != EPI_STATS && epi != EPI_STATS16;
+    return can_half && ((M + G2_BM - 1) / G2_BM) * ((N + bn - 1) / bn) * slabs < 512 ? 64 : G2_BM;
+}
+// dgx_gemm_lds_bf16's checks of the shape arguments, in its order: the part
+// before the empty-output return (a_k: 0 becomes K) ...
+inline int lds_check_k(int tn, int M, int N, int K, int& a_k, int splits) {
+    if (M < 0 || N < 0 || K < 0 || splits < 1) return DGX_EINVAL;
+    if (a_k == 0) a_k = K;
+    if (a_k != K && (tn || a_k < G2_BK || a_k % G2_BK || K % a_k)) return DGX_EUNSUPPORTED;
+    return DGX_OK;
+}
+// ... and the part after it
+inline int lds_check_form(int tn, int M, int N, int K, int epi) {
+    if (tn ? (M < 8 || N < 8 || M % 8 || N % 8 || epi != EPI_SLAB) : (K % G2_BK || epi == EPI_SLAB))
+        return DGX_EUNSUPPORTED;
+    if (!tn && epi != EPI_STORE && epi != EPI_ACCUM && epi != EPI_STATS && epi != EPI_STATS16) return DGX_EUNSUPPORTED;
+    return DGX_OK;
+}
+
 template <bool TN, int BN, int EPI>
 int launch_gemm_lds(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, int M, int N, int K, int ka, int splits,
                     float* C, int64_t ldc, float* part, const float* addend, int64_t ldd, hipStream_t st) {
     const auto [kchunk, sp] = dgx_split_k(K, splits, G2_BK);
     const int nJ = (N + BN - 1) / BN;
-    // skinny outputs (few 128-row tiles): 64-row tiles double the workgroups so
-    // two share each CU and hide each other's load latency
     constexpr bool can_half = EPI != EPI_STATS && EPI != EPI_STATS16;
-    const bool half = can_half && ((M + G2_BM - 1) / G2_BM) * nJ * sp < 512;
+    const bool half = lds_bm(M, N, BN, sp, EPI) == 64;
     if constexpr (can_half) {
         if (half) {
             const int nI = (M + 63) / 64;
@@ -1435,6 +1465,16 @@ int dgx_gemm_splits(int M, int N, int K) {
 int dgx_gemm_slabs(int K, int splits) { return dgx_split_k(K, splits, GB_BK).slabs; }
 int dgx_gemm_lds_slabs(int K, int splits) { return dgx_split_k(K, splits, G2_BK).slabs; }
 
+int dgx_gemm_lds_tile(int tn, int M, int N, int K, int a_k, int epi, int splits) {
+    if (const int rc = lds_check_k(tn, M, N, K, a_k, splits)) return rc;
+    if (M == 0 || N == 0) return 0;  // DGX_OK without a launch
+    if (const int rc = lds_check_form(tn, M, N, K, epi)) return rc;
+    if (!tn && lds_big(M, N, K, a_k)) return G3_BM * 1000 + G3_BN;
+    const int bn = lds_bn(N);
+    const int slabs = tn ? dgx_split_k(K, splits, G2_BK).slabs : 1;  // NT launches never split
+    return lds_bm(M, N, bn, slabs, epi) * 1000 + bn;
+}
+
 int dgx_gemm_bf16(const void* A, int a_bf16, int a_ic, int64_t lda, const void* B, int b_bf16, int b_ic,
                   int64_t ldb, int M, int N, int K, int epi, int splits, float* C, int64_t ldc, float* partials,
                   void* stream) {
@@ -1526,10 +1566,7 @@ int dgx_gemm_h1bwd_bf16(const void* dZ2, const void* W2t, int M, int N, int K, c
 
 // BM of the EPI_EDZ launch: 64-row tiles when 128-row ones would leave fewer
 // than 512 workgroups (launch_gemm_lds's skinny rule)
-inline int edz_bm(int M, int N) {
-    const int bn = N > 64 ? 128 : 64;
-    return (int64_t)((M + G2_BM - 1) / G2_BM) * ((N + bn - 1) / bn) < 512 ? 64 : G2_BM;
-}
+inline int edz_bm(int M, int N) { return lds_bm(M, N, lds_bn(N), 1, EPI_EDZ); }
 
 int dgx_gemm_edge_dz_rows(int M, int N) {
     if (M < 1 || N < 1) return DGX_EINVAL;
@@ -1578,30 +1615,24 @@ int dgx_gemm_edge_dz_bf16(const void* A, int64_t lda, const void* W, int64_t ldw
 int dgx_gemm_lds_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, int tn, int M, int N, int K,
                       int a_k, int epi, int splits, float* C, int64_t ldc, float* partials, const float* addend,
                       int64_t ldd, void* stream) {
-    if (!A || !B || !C || M < 0 || N < 0 || K < 0 || splits < 1) return DGX_EINVAL;
-    if (a_k == 0) a_k = K;
-    if (a_k != K && (tn || a_k < G2_BK || a_k % G2_BK || K % a_k)) return DGX_EUNSUPPORTED;
+    if (!A || !B || !C) return DGX_EINVAL;
+    if (const int rc = lds_check_k(tn, M, N, K, a_k, splits)) return rc;
     if ((epi == EPI_STATS || epi == EPI_STATS16) && !partials) return DGX_EINVAL;
     if (M == 0 || N == 0) return DGX_OK;
     // DMA staging moves 16-B chunks: rows 16-B aligned, whole chunks per row
     if (!aligned_to(A, 16) || !aligned_to(B, 16) || lda % 8 || ldb % 8) return DGX_EUNSUPPORTED;
-    if (tn ? (M < 8 || N < 8 || M % 8 || N % 8 || epi != EPI_SLAB) : (K % G2_BK || epi == EPI_SLAB))
-        return DGX_EUNSUPPORTED;
+    if (const int rc = lds_check_form(tn, M, N, K, epi)) return rc;
     if (epi == EPI_SLAB) ldc = N;
     hipStream_t st = dgx_stream(stream);
     const bf16* a = static_cast<const bf16*>(A);
     const bf16* b = static_cast<const bf16*>(B);
-    const bool wide = N > 64;
+    const bool wide = lds_bn(N) == 128;
     if (tn)
         return wide ? launch_gemm_lds<true, 128, EPI_SLAB>(a, lda, b, ldb, M, N, K, K, splits, C, ldc, partials,
                                                            nullptr, 0, st)
                     : launch_gemm_lds<true, 64, EPI_SLAB>(a, lda, b, ldb, M, N, K, K, splits, C, ldc, partials, nullptr,
                                                           0, st);
-    // large NT GEMMs (conv5 forward and input gradient): 256 x 256 tiles when
-    // they fill the chip (>= 256 tiles) and every tile is whole along N and K
-    const bool big = (int64_t)((M + G3_BM - 1) / G3_BM) * ((N + G3_BN - 1) / G3_BN) >= 256 && N % G3_BN == 0 &&
-                     K % G3_BK == 0 && a_k % G3_BK == 0;
-    if (big) {
+    if (lds_big(M, N, K, a_k)) {
         if (epi == EPI_STORE) return launch_gemm256<EPI_STORE>(a, lda, b, ldb, M, N, K, a_k, C, ldc, partials, addend,
                                                               ldd, st);
         if (epi == EPI_ACCUM) return launch_gemm256<EPI_ACCUM>(a, lda, b, ldb, M, N, K, a_k, C, ldc, partials, addend,

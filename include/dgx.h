@@ -459,6 +459,12 @@ int dgx_gemm_lds_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, in
                       int M, int N, int K, int a_k, int epi, int splits, float* C,
                       int64_t ldc, float* partials, const float* addend,
                       int64_t ldd, void* stream);
+/* The tile dgx_gemm_lds_bf16 launches for these shape arguments, as
+ * BM * 1000 + BN (256256: the 256 x 256 kernel; 128 or 64 rows x 128 or 64
+ * columns otherwise), 0 for an empty output (M or N == 0: no launch), or the
+ * negative code its shape checks return. Host arithmetic only: the launcher
+ * takes its decision from the same functions. */
+int dgx_gemm_lds_tile(int tn, int M, int N, int K, int a_k, int epi, int splits);
 /* fp32 (rows x cols, row stride lds) -> two bf16 planes (row stride ldo): hi =
  * bf16(x) (nullable: skip), lo = bf16(x - hi) — x with 16 significant bits as
  * hi + lo. The operands of the fp32 parity mode's 3-pass GEMMs (hi.W_hi +

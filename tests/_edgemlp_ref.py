@@ -90,6 +90,8 @@ The lattice cases carry exactness; the random cases prove range and rounding.
 """
 import torch
 
+from _gemm_ref import Buf
+
 U = 2.0 ** -24
 SENT = 12288.0          # exactly representable in bf16 and fp32
 LIM = float(2 ** 24)
@@ -579,9 +581,10 @@ SCATTER_GRID = [
 # ---- helpers of the GPU tests -------------------------------------------------
 
 def guarded(rows, cols, dev, dtype=torch.float32, fill=SENT):
-    """(buffer of rows + 1 canary row, all `fill`; view of the rows)"""
-    full = torch.full((rows + 1, cols), fill, dtype=dtype, device=dev)
-    return full, full[:rows]
+    """(buffer of rows + 1 canary row, all `fill`; view of the rows): the
+    dense one-guard-row form of the GEMM tests' Buf (tests/_gemm_ref.py)"""
+    b = Buf(rows, cols, dev, dtype, fill, guard_rows=1)
+    return b.full, b.view
 
 
 def guard_intact(full, fill=SENT):
