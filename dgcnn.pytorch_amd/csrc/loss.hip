@@ -39,43 +39,15 @@
 // A label is only compared with the class index, never used as an address: an
 // out-of-range label matches no class and makes that row's loss and gradient
 // NaN (a GradScaler then skips the step).
-#include <hip/hip_fp16.h>
-
 #include <algorithm>
 
-#include "common.h"
+#include "ce_row.h"
 
 namespace {
 
 constexpr int CE_ROWS = 128;            // rows per workgroup = threads per workgroup
 constexpr int CE_TILE_BYTES = 32768;    // LDS staging of the rows kernel
-constexpr int CE_BATCH = 8;              // logits a lane loads ahead of their use
 constexpr int CE_MIN_TILE_ROWS = 32;    // narrower tiles leave most lanes idle: read global memory instead
-
-template <int DT> struct Elt;
-template <> struct Elt<DGX_CE_F32> {
-    using T = float;
-    static __device__ __forceinline__ float ld(const T* p) { return *p; }
-    static __device__ __forceinline__ T cv(float v) { return v; }
-};
-template <> struct Elt<DGX_CE_F16> {
-    using T = uint16_t;
-    static __device__ __forceinline__ float ld(const T* p) { return __half2float(__ushort_as_half(*p)); }
-    static __device__ __forceinline__ T cv(float v) { return __half_as_ushort(__float2half_rn(v)); }
-};
-template <> struct Elt<DGX_CE_BF16> {
-    using T = uint16_t;
-    static __device__ __forceinline__ float ld(const T* p) { return __uint_as_float((uint32_t)*p << 16); }
-    static __device__ __forceinline__ T cv(float v) {   // round to nearest even; NaN stays NaN
-        const uint32_t u = __float_as_uint(v);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (T)((u >> 16) | 0x40u);
-        return (T)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
-};
-
-__device__ __forceinline__ int64_t ce_label(const void* labels, int l64, int64_t row) {
-    return l64 ? static_cast<const int64_t*>(labels)[row] : (int64_t) static_cast<const int32_t*>(labels)[row];
-}
 
 // exp(-d) for d >= 0 in fp64, relative error about 1e-13 (the gradient needs lse to about 1e-10):
 // -d = n ln 2 + r with |r| <= ln 2 / 2, a degree-10 Taylor polynomial in r, scaled by 2^n.
@@ -107,22 +79,10 @@ struct CeRow {
 // One row; ld(j) is logit j as fp32. The first maximum wins the arg-max.
 template <class Ld>
 __device__ __forceinline__ CeRow ce_row(Ld ld, int C, int64_t y, float w_true, float w_other, double W) {
-    // both passes fetch CE_BATCH logits before they use them: one lane walks a whole row, and a
-    // load waited for at every class leaves the row bound by memory latency
-    float mx = ld(0);
-    int arg = 0;
-    for (int j0 = 0; j0 < C; j0 += CE_BATCH) {
-        float v[CE_BATCH];
-#pragma unroll
-        for (int u = 0; u < CE_BATCH; ++u) v[u] = ld(min(j0 + u, C - 1));
-#pragma unroll
-        for (int u = 0; u < CE_BATCH; ++u) {
-            if (j0 + u < C && v[u] > mx) {
-                mx = v[u];
-                arg = j0 + u;
-            }
-        }
-    }
+    // both passes fetch CE_BATCH logits before they use them (see ce_row_max)
+    float mx;
+    int arg;
+    ce_row_max(ld, C, mx, arg);
     double S = 0.0, T = 0.0;
     bool found = false;
     for (int j0 = 0; j0 < C; j0 += CE_BATCH) {
@@ -187,21 +147,8 @@ __global__ __launch_bounds__(CE_ROWS) void ce_fwd_rows_kernel(const typename Elt
             const int tr = min(tile_rows, nrows - t0);
             // rows [r0 + t0, r0 + t0 + tr) are the bytes [beg, end); stage the 16-byte granules that cover them
             const uintptr_t beg = reinterpret_cast<uintptr_t>(x + (r0 + t0) * C);
-            const uintptr_t end = beg + (size_t)tr * C * sizeof(T);
             const uintptr_t a0 = beg & ~(uintptr_t)15;
-            // granules [first, full) lie inside the range: 16-byte loads, four in flight per lane
-            const int first = beg == a0 ? 0 : 1, full = (int)((end - a0) >> 4);   // full <= CE_TILE_BYTES / 16 + 1
-#pragma unroll 4
-            for (int q = first + tid; q < full; q += CE_ROWS)
-                *reinterpret_cast<uint4*>(tile + (q << 4)) = *reinterpret_cast<const uint4*>(a0 + ((uintptr_t)q << 4));
-            // the granule in front of them and the one behind: only the elements inside the range
-            if (tid < 2) {
-                const uintptr_t src = tid == 0 ? a0 : a0 + ((uintptr_t)full << 4);
-                const uintptr_t lo = src > beg ? src : beg, hi = src + 16 < end ? src + 16 : end;
-                if (tid == 1 || first == 1)
-                    for (uintptr_t o = lo; o < hi; o += sizeof(T))
-                        *reinterpret_cast<T*>(tile + (o - a0)) = *reinterpret_cast<const T*>(o);
-            }
+            ce_stage_rows<T, CE_ROWS>(tile, beg, (size_t)tr * C * sizeof(T), tid);
             __syncthreads();
             if (tid < tr) {
                 const int64_t row = r0 + t0 + tid;

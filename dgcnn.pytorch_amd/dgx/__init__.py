@@ -3,9 +3,11 @@
 Python surface:
   ops.knn / ops.graph_feature     drop-ins for reference models/dgcnn.py:6-44
   edgeconv.edgeconv_stack         the fused DGCNN block chain (dgcnn.py:84-100)
+  metrics.SegMetrics              the scripts' per-step and epoch-end metrics, accumulated on the device
 """
 from . import _native  # noqa: F401
 from .ops import knn, graph_feature, reduction_order  # noqa: F401
 from .edgeconv import edgeconv_stack  # noqa: F401
+from . import metrics  # noqa: F401
 
-__all__ = ["knn", "graph_feature", "reduction_order", "edgeconv_stack"]
+__all__ = ["knn", "graph_feature", "reduction_order", "edgeconv_stack", "metrics"]

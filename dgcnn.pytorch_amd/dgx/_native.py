@@ -147,6 +147,9 @@ _SIGS = {
     "dgx_smoothed_ce_fwd": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp,
                             _sz, _vp],
     "dgx_smoothed_ce_bwd": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp],
+    "dgx_seg_metrics_max_classes": [],
+    "dgx_seg_metrics_update": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
+                               _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "dgx_version": ctypes.c_char_p,

@@ -241,6 +241,61 @@ def smoothed_cross_entropy(logits, target, smoothing=True, eps=0.2, return_pred=
     return (loss, logits.detach().max(dim=1)[1]) if return_pred else loss
 
 
+def seg_argmax(scores):
+    """Arg-max over dim 1 with the loss head's rule (csrc/ce_row.h): the
+    smallest index among equal maxima; a NaN never compares greater, so a row
+    whose logit 0 is NaN keeps class 0 and a NaN elsewhere is passed over
+    (torch's own max treats a NaN as the maximum)."""
+    x = scores.detach().float()
+    nan = torch.isnan(x)
+    arg = torch.where(nan, torch.full_like(x, float("-inf")), x).argmax(dim=1)
+    return torch.where(nan.select(1, 0), torch.zeros_like(arg), arg)
+
+
+def seg_metrics_update(scores, seg, cat, part_start, part_count, confusion, iu, nparts, state, loss, loss_sum):
+    """dgx_seg_metrics_update (include/dgx.h) with torch ops, on the state
+    tensors of dgx.metrics.SegMetrics in place: ``scores`` (B, C, N) logits or
+    (B, N) class ids, ``seg`` (B, N), ``cat`` (B,) or None. Each shape's
+    (true, pred) pairs are counted as a bincount of ``true * C + pred`` (a
+    scatter-add into a (B, C * C) table); invalid labels, categories and
+    shapes beyond the capacity are counted as the kernel counts them."""
+    C = confusion.shape[0]
+    pred = seg_argmax(scores) if scores.is_floating_point() else scores.long()
+    B = seg.shape[0]
+    true, pred = seg.long().reshape(B, -1), pred.reshape(B, -1)
+    ok = (true >= 0) & (true < C) & (pred >= 0) & (pred < C)
+    flat = torch.where(ok, true * C + pred, torch.zeros_like(true))
+    per = torch.zeros(B, C * C, dtype=torch.int64, device=seg.device).scatter_add_(1, flat, ok.long())
+    confusion += per.sum(dim=0).view(C, C)
+    invalid = (~ok).sum()
+    if cat is not None:
+        cat = cat.long().reshape(B)
+        capacity, max_parts = iu.shape[0], iu.shape[1]
+        cat_ok = (cat >= 0) & (cat < part_start.numel())
+        c = torch.where(cat_ok, cat, torch.zeros_like(cat))
+        start, count = part_start.long()[c], part_count.long()[c]
+        cat_ok = cat_ok & (start >= 0) & (count >= 0) & (count <= max_parts) & (start <= C - count)
+        count = torch.where(cat_ok, count, torch.zeros_like(count))
+        invalid = invalid + (~cat_ok).sum()
+        table = per.view(B, C, C)
+        inter = table.diagonal(dim1=1, dim2=2)
+        union = table.sum(dim=2) + table.sum(dim=1) - inter           # rowsum + colsum - I
+        q = torch.arange(max_parts, device=seg.device)
+        live = q[None, :] < count[:, None]
+        part = torch.where(live, start[:, None] + q[None, :], torch.zeros_like(live, dtype=torch.int64))
+        rec = torch.stack([inter.gather(1, part), union.gather(1, part)], dim=2) * live[:, :, None]
+        slot = state[0] + torch.arange(B, device=seg.device)
+        fits = (slot >= 0) & (slot < capacity)
+        iu[slot[fits]] = rec[fits].to(iu.dtype)
+        nparts[slot[fits]] = count[fits].to(nparts.dtype)
+        state[2] += (~fits).sum()
+        state[0] += B
+    state[1] += invalid
+    state[3] += B
+    if loss is not None:
+        loss_sum.copy_(loss_sum + loss.detach().to(torch.float32).reshape(loss_sum.shape))
+
+
 def attention(q, k, v, heads, dropout_p=0.0, scale=None):
     """dropout(softmax(scale q k^T)) v per head on the host (torch's
     scaled_dot_product_attention, the kernel nn.MultiheadAttention uses)."""

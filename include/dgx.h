@@ -745,6 +745,50 @@ int dgx_smoothed_ce_bwd(const void* logits, int dtype, int64_t B, int64_t C, int
                         int64_t sn, const void* labels, int label_is_i64, float w_true, float w_other,
                         const double* lse, const float* g, void* dlogits, void* stream);
 
+/* ---- segmentation / classification metrics accumulated on the device (the
+ * reference's per-step host bookkeeping, main_partseg_dist.py:259-274, and its
+ * epoch-end calculate_shape_IoU / calculate_sem_IoU / accuracy scores). One
+ * call consumes one batch in one launch and only adds integers to the
+ * caller's state; the ratios are taken on the host from those integers.
+ *
+ * Predictions (dtype): logits in dgx_smoothed_ce_fwd's dtypes (DGX_CE_*) and
+ * its two layouts of a (B, C, N) tensor with strides (sb, sc, sn), whose
+ * arg-max is taken with the loss head's rule (same classes as its pred, bit
+ * for bit); or ready class ids (B, N), int64 / int32 (DGX_SEG_PRED_*; the
+ * strides are not read). seg: the true classes (B, N), int64 or int32.
+ * 2 <= C <= dgx_seg_metrics_max_classes(), else DGX_EUNSUPPORTED.
+ *
+ * cat (NULL: none), int64 or int32, length B, is each shape's category; parts
+ * part_start[c] .. part_start[c] + part_count[c] - 1 of the class range belong
+ * to category c (device tables of ncat int32 each). With cat, shape b of the
+ * call is recorded at slot s = cursor + b while s < capacity:
+ *   nparts[s] = part_count[c];  iu[s][q][0] = I, iu[s][q][1] = U for part slot
+ *   q < nparts[s] (points with pred == part and / or seg == part), 0 beyond;
+ *   iu is int32 [capacity][max_parts][2].
+ * confusion is int64 [C][C], indexed [true][pred], of all points of all calls.
+ * state is DGX_SEG_STATE_WORDS int64 words:
+ *   [0] cursor    shapes offered so far (advanced by B per call with cat)
+ *   [1] invalid   points whose seg or integer prediction is outside [0, C),
+ *                 shapes whose cat is outside [0, ncat) or whose part range
+ *                 does not fit the class range or max_parts; none of them is
+ *                 counted or used as an address (such a shape's points still
+ *                 count in the confusion table; its slot gets nparts = 0)
+ *   [2] overflow  shapes at slots >= capacity, not written
+ *   [3] count     += B per call
+ *   [4] ticket    0 between calls (the kernel's own)
+ * With loss (a device fp32 scalar; NULL: none) *loss_sum = *loss_sum + *loss
+ * in fp32. The caller zeroes confusion, state and loss_sum to start an epoch.
+ * Calls on one state must be ordered (one stream, or a linear graph). */
+#define DGX_SEG_PRED_I64 3
+#define DGX_SEG_PRED_I32 4
+#define DGX_SEG_STATE_WORDS 8
+int dgx_seg_metrics_max_classes(void);
+int dgx_seg_metrics_update(const void* scores, int dtype, int64_t B, int64_t C, int64_t N, int64_t sb, int64_t sc,
+                           int64_t sn, const void* seg, int seg_is_i64, const void* cat, int cat_is_i64,
+                           const int32_t* part_start, const int32_t* part_count, int ncat, int64_t* confusion,
+                           int32_t* iu, int32_t* nparts, int64_t capacity, int max_parts, int64_t* state,
+                           const float* loss, float* loss_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
