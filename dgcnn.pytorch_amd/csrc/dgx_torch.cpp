@@ -72,23 +72,22 @@ int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // A/B switches of the schedule (dgx.edgeconv / dgx.gemm environment flags), one word:
 // bit i is switch kOptNames[i] (dgx.schedule.OPT_BITS), bits 8-15 the slab cap
-enum OptBit { kScatterPacked, kFoldBnBwd, kFuseKnnImage, kFuseEdgeDz, kSplit32, kScatterPush, kSplit32Edge, kNumOptBits };
+enum OptBit { kScatterPacked, kFoldBnBwd, kFuseKnnImage, kFuseEdgeDz, kSplit32, kSplit32Edge, kNumOptBits };
 const char* const kOptNames[kNumOptBits] = {"SCATTER_PACKED", "FOLD_BN_BWD", "FUSE_KNN_IMAGE", "FUSE_EDGE_DZ",
-                                            "SPLIT32",        "SCATTER_PUSH", "SPLIT32_EDGE"};
+                                            "SPLIT32",        "SPLIT32_EDGE"};
 struct Opts {                // one member per OptBit, in that order, then the slab cap
   bool packed;               // bf16 / split fp32: backward scatter reads packed dz|slot words
   bool fold_bwd;             // BN backward finalize in the scatter's prologue
   bool fuse_image;           // blocks' apply writes the next kNN's operand image
   bool fuse_edge_dz;         // bf16: block l-1's dz from block l's dX GEMM epilogue
   bool split32;              // fp32 mode: conv5 GEMMs as 3-pass split bf16 (hi.hi + hi.lo + lo.hi)
-  bool push;                 // backward scatter: selected-edge dz pushed from the sources (fixed-point LDS sums)
   bool split_edge;           // with split32: EdgeConv dW / dX as 3-pass split bf16 on the scatter's split dPQ planes
   int64_t slab_cap_mb;       // split-K slab cap of small weight gradients (0 = off)
 };
 Opts decode(int64_t o) {
   auto bit = [o](OptBit b) { return ((o >> b) & 1) != 0; };
   return Opts{bit(kScatterPacked), bit(kFoldBnBwd),  bit(kFuseKnnImage), bit(kFuseEdgeDz), bit(kSplit32),
-              bit(kScatterPush),   bit(kSplit32Edge), (o >> 8) & 0xff};
+              bit(kSplit32Edge),   (o >> 8) & 0xff};
 }
 
 struct Dev {
@@ -790,10 +789,9 @@ ChainOut chain_forward_impl(const Dev& d, const Tensor& x_in, int k, std::vector
   const int n = (int)L.size();
   int64_t total = 0;
   for (auto& ly : L) total += ly.co;
-  if (need_grad && !o.push) {
+  if (need_grad) {
     // the backward's pull scatter stages a cloud's one-channel slices in LDS: a
-    // cloud it cannot take is refused here, before the forward has run
-    // (the push form, o.push, has its own geometry and refuses in the backward).
+    // cloud it cannot take is refused here, before the forward has run.
     // One block stands for all: the scatter doubles its point parts until the
     // slice fits or parts * 64 >= N, an end state the channel count does not change.
     const int pk = (bf16 || o.split32) && o.packed;
@@ -976,7 +974,7 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
     std::vector<PrepJob> jobs;
     std::vector<int> at;
     for (int l = 1; l < n; ++l) {
-      esplit[l] = o.split32 && o.split_edge && packed && !o.push && L[l].cin % 64 == 0 && L[l].co % 32 == 0 &&
+      esplit[l] = o.split32 && o.split_edge && packed && L[l].cin % 64 == 0 && L[l].co % 32 == 0 &&
                   L[l].w.is_contiguous();
       if (esplit[l]) {
         jobs.push_back(PrepJob{L[l].w, L[l].co, L[l].cin, true, false, true});
@@ -1001,7 +999,7 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
     const int cin = ly.cin, co = ly.co;
     off -= co;
     const int64_t prev = li > 0 ? off - L[li - 1].co : 0;
-    const Tensor &idx = field(saved, li, kIdx), &PQ = field(saved, li, kPQ), &ysel = field(saved, li, kYsel),
+    const Tensor &PQ = field(saved, li, kPQ), &ysel = field(saved, li, kYsel),
                  &arg = field(saved, li, kArg), &sumP = field(saved, li, kSumP);
     const Stats& st = stats[li];
     const Tensor X = li == 0 ? x_pm : xcat.narrow(1, prev, cin);
@@ -1053,14 +1051,7 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
       c0 = at::empty({co}, d.f32);
       c1 = at::empty({co}, d.f32);
     }
-    if (fold && o.push) {   // BN backward finalize in the push scatter's prologue (one launch)
-      check(dgx_edge_bwd_scatter_push_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(idx), P<int32_t>(rowptr[li]),
-                                          P<int32_t>(edges[li]), P(dz), packed ? nullptr : P<uint8_t>(arg), P(sumP),
-                                          B, N, k, co, P(partials), nblk, count, P(st.scale), P(st.mean),
-                                          P(st.invstd), (int)st.eval, P(dgamma), P(dbeta), P(c0), P(c1),
-                                          dPQ.data_ptr(), out_mode, (int)packed, d.stream),
-            "edge bwd scatter");
-    } else if (fold) {   // BN backward finalize in the scatter's prologue (one launch)
+    if (fold) {   // BN backward finalize in the scatter's prologue (one launch)
       check(dgx_edge_bwd_scatter_fin_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(rowptr[li]), P<int32_t>(edges[li]), P(dz),
                                          packed ? nullptr : P<uint8_t>(arg), P(sumP), B, N, k, co, P(partials), nblk,
                                          count, P(st.scale), P(st.mean), P(st.invstd), (int)st.eval, P(dgamma), P(dbeta),
@@ -1072,13 +1063,7 @@ ChainGrads chain_backward_impl(const Dev& d, Tensor dxcat, bool dxcat_owned, con
       dbeta = r[1];
       c0 = r[2];
       c1 = r[3];
-      if (o.push)
-        check(dgx_edge_bwd_scatter_push_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(idx), P<int32_t>(rowptr[li]),
-                                            P<int32_t>(edges[li]), P(dz), packed ? nullptr : P<uint8_t>(arg), P(sumP),
-                                            B, N, k, co, nullptr, 0, 0.0, P(st.scale), nullptr, nullptr, 0, nullptr,
-                                            nullptr, P(c0), P(c1), dPQ.data_ptr(), out_mode, (int)packed, d.stream),
-              "edge bwd scatter");
-      else if (packed)
+      if (packed)
         check(dgx_edge_bwd_scatter_packed_f32(P(PQ), (int)PQ.stride(0), P<int32_t>(rowptr[li]), P<int32_t>(edges[li]),
                                               P(dz), P(sumP), B, N, k, co, P(st.scale), P(c0), P(c1), dPQ.data_ptr(),
                                               out_mode, d.stream),

@@ -75,8 +75,6 @@ _SIGS = {
                                      _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp],
     "dgx_edge_bwd_scatter_packed_f32": [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                         _i32, _vp],
-    "dgx_edge_bwd_scatter_push_f32": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32,
-                                      _f64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp],
     "dgx_colstats_rows": [_i64],
     "dgx_colstats_f32": [_vp, _i32, _i64, _i32, _vp, _i32, _vp],
     "dgx_pointconv_apply_f32": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _vp, _vp],

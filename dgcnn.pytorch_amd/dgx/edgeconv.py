@@ -66,13 +66,6 @@ SPLIT32 = os.environ.get("DGX_SPLIT32", "0") == "1"
 # backward scatter writes dPQ as its split planes and dW / dX run as the same
 # 3-pass GEMMs (DGX_SPLIT32_EDGE=0: those two on the f32 MFMA)
 SPLIT32_EDGE = os.environ.get("DGX_SPLIT32_EDGE", "1") == "1"
-# backward scatter in push form (dgx_edge_bwd_scatter_push_f32): each source's
-# selected dz is added to its target in exact 64-bit fixed point (order-free,
-# the exact sum rounded once), the in-edge loop reads only Q rows. Measured
-# slower than the pull form (cfg2 step 1.32 -> 1.41 ms, r06u): the scatter is
-# bound by its per-workgroup latency chain, which the push phases lengthen.
-# DGX_SCATTER_PUSH=1 selects it.
-SCATTER_PUSH = os.environ.get("DGX_SCATTER_PUSH", "0") == "1"
 
 
 def debug_capture():

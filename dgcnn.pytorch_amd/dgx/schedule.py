@@ -31,8 +31,7 @@ EMLP_FIELDS = ("X", "idx", "PQ", "sumP", "H1", "Z2", "ysel", "arg", "scale1", "s
                "scale2", "shift2", "mean2", "invstd2", "nt", "tn")
 # bit i of the opts word is the A/B switch of this name (module attributes of
 # dgx.edgeconv, documented there); bits 8-15 carry gemm.SLAB_CAP_MB
-OPT_BITS = ("SCATTER_PACKED", "FOLD_BN_BWD", "FUSE_KNN_IMAGE", "FUSE_EDGE_DZ", "SPLIT32", "SCATTER_PUSH",
-            "SPLIT32_EDGE")
+OPT_BITS = ("SCATTER_PACKED", "FOLD_BN_BWD", "FUSE_KNN_IMAGE", "FUSE_EDGE_DZ", "SPLIT32", "SPLIT32_EDGE")
 
 ChainBlock = namedtuple("ChainBlock", CHAIN_FIELDS)
 PcSaved = namedtuple("PcSaved", PC_FIELDS)

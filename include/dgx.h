@@ -259,8 +259,7 @@ int dgx_graph_reverse_multi(int n, const int32_t* const* idx, int B, int N, int 
                             int32_t* const* rowptr, int32_t* const* edges, void* stream);
 /* dPQ output (out_bf16): 0 fp32, 1 bf16, 2 split bf16 planes — hi = bf16(v)
  * at dPQ, lo = bf16(v - hi) at dPQ + B*N*2Co elements — or 3: (hi, lo, hi),
- * hi again at dPQ + 2*B*N*2Co (the fp32 mode's 3-pass GEMM operands; the pull
- * forms below, not the push form). */
+ * hi again at dPQ + 2*B*N*2Co (the fp32 mode's 3-pass GEMM operands). */
 int dgx_edge_bwd_scatter_f32(const float* PQ, int ldpq, const int32_t* rowptr,
                              const int32_t* edges, const float* dz,
                              const uint8_t* arg, const float* sumP, int B, int N,
@@ -293,21 +292,6 @@ int dgx_edge_bwd_scatter_packed_f32(const float* PQ, int ldpq, const int32_t* ro
                                     const float* sumP, int B, int N, int k, int Co,
                                     const float* scale, const float* c0, const float* c1,
                                     void* dPQ, int out_bf16, void* stream);
-/* The same dPQ with the selected-edge term pushed from the sources: each
- * (point i, channel c) adds dz_i[c] to j = idx[i][slot] (idx: the forward's
- * B x N x k kNN graph), summed exactly in 64-bit fixed point (LDS atomics,
- * order-independent, rounded once to fp32), so the in-edge loop reads Q rows
- * only. All modes in one entry: partials != NULL finalizes the BN backward as
- * dgx_edge_bwd_scatter_fin_f32 (else c0 / c1 are inputs, eval ignored);
- * packed != 0 reads dgx_edge_bwd_dz_packed_f32 words (arg unused). A channel
- * whose dz holds inf / NaN gets NaN in every dP of the channel. */
-int dgx_edge_bwd_scatter_push_f32(const float* PQ, int ldpq, const int32_t* idx,
-                                  const int32_t* rowptr, const int32_t* edges, const float* dz,
-                                  const uint8_t* arg, const float* sumP, int B, int N, int k,
-                                  int Co, const float* partials, int nrows, double count,
-                                  const float* scale, const float* mean, const float* invstd,
-                                  int eval, float* dgamma, float* dbeta, float* c0, float* c1,
-                                  void* dPQ, int out_bf16, int packed, void* stream);
 
 /* ---- a4: pointwise Conv1x1 + BatchNorm + LeakyReLU, replaces conv5 of
  * models/dgcnn.py:74-78, 100-102 (cat(x1..x4) -> Conv2d(512,emb,1) -> BN ->

@@ -282,21 +282,18 @@ def _flags(bf16, add=(), drop=()):
 # kernels from these flags alone: fp32 -> dgx_edge_bwd_dz_f32 + the pull
 # scatter with dz and slot bytes (fp32 dPQ); bf16 / split -> packed dz|slot
 # words, bf16 / split-plane dPQ; FOLD_BN_BWD -> dgx_edge_bwd_scatter_fin_f32,
-# else the separate finalize + dgx_edge_bwd_scatter[_packed]_f32; SCATTER_PUSH
-# -> dgx_edge_bwd_scatter_push_f32; two bf16 blocks -> dgx_gemm_edge_dz_bf16
-# writes block 1's packed dz (its further conditions: _gemm_dz_route). One
+# else the separate finalize + dgx_edge_bwd_scatter[_packed]_f32; two bf16
+# blocks -> dgx_gemm_edge_dz_bf16 writes block 1's packed dz (its further conditions: _gemm_dz_route). One
 # cloud stored channel-major takes the same kernels: its point-major rows are a
 # column-major view (tests/test_batch1_gpu.py), which the GEMMs must still read
 # as rows. (dgx_edge_bwd_dz_cm_f32 is the edge MLP's: see its backward test.)
 EDGE_VARIANTS = {
     "fp32_fin": _Variant("fp32", flags=(False, (), ())),
     "fp32_unfolded": _Variant("fp32", switches={"FOLD_BN_BWD": False}, flags=(False, (), ("FOLD_BN_BWD",))),
-    "fp32_push": _Variant("fp32", switches={"SCATTER_PUSH": True}, flags=(False, ("SCATTER_PUSH",), ())),
     "fp32_split_planes": _Variant("fp32_split", flags=(False, ("SPLIT32",), ())),
     "bf16_packed_fin": _Variant("bf16", flags=(True, (), ())),
     "bf16_packed_unfolded": _Variant("bf16", switches={"FOLD_BN_BWD": False}, flags=(True, (), ("FOLD_BN_BWD",))),
     "bf16_slot_bytes": _Variant("bf16", switches={"SCATTER_PACKED": False}, flags=(True, (), ("SCATTER_PACKED",))),
-    "bf16_push": _Variant("bf16", switches={"SCATTER_PUSH": True}, flags=(True, ("SCATTER_PUSH",), ())),
     "bf16_two_blocks_gemm_dz": _Variant("bf16", widths=(64, 64, 128), flags=(True, (), ())),
     "eval_fp32": _Variant("fp32", train=False, flags=(False, (), ())),
     "eval_bf16": _Variant("bf16", train=False, flags=(True, (), ())),
@@ -519,9 +516,9 @@ def _scatter_out_nonfinite(out, S, row, ch):
 @pytest.mark.parametrize("packed", [False, True])
 def test_scatter_entries_keep_nonfinite_dz(cuda, packed):
     """Every backward-scatter entry of the C ABI on a dz with one inf (slot bits
-    kept in a packed word): pull (fp32, bf16, split planes 2 / 3), the finalize-
-    in-prologue pull and push (fp32 / bf16, c0 / c1 given or finalized)."""
-    import test_scatter_push_gpu as SP
+    kept in a packed word): c0 / c1 given (fp32, bf16, split planes 2 / 3) and
+    finalized in the prologue (fp32, bf16)."""
+    import test_scatter_gpu as SP
     from dgx import _native as nat
     S = SP._setup(cuda, 2, 300, 11, 20, seed=9, packed=packed)
     L, st, M, Co = S["L"], S["st"], S["M"], S["Co"]
@@ -545,10 +542,6 @@ def test_scatter_entries_keep_nonfinite_dz(cuda, packed):
                       "scatter")
         _scatter_out_nonfinite(planes[0], S, row, ch)          # the hi plane (mode 1: the bf16 output)
         reached.append(f"pull_mode{mode}")
-    for bf16 in (False, True):
-        for fin in (False, True):
-            _scatter_out_nonfinite(SP._push(S, packed, bf16=bf16, fin=fin)[0], S, row, ch)
-            reached.append(f"push_bf16{int(bf16)}_fin{int(fin)}")
     for mode in (0, 1):
         out = torch.zeros(M, 2 * Co, device=cuda, dtype=torch.bfloat16 if mode else torch.float32)
         o = [torch.empty(Co, device=cuda) for _ in range(4)]
@@ -561,8 +554,7 @@ def test_scatter_entries_keep_nonfinite_dz(cuda, packed):
         _scatter_out_nonfinite(out, S, row, ch)
         reached.append(f"fin_mode{mode}")
     torch.cuda.synchronize()
-    assert reached == ["pull_f32", "pull_mode1", "pull_mode2", "pull_mode3", "push_bf160_fin0", "push_bf160_fin1",
-                       "push_bf161_fin0", "push_bf161_fin1", "fin_mode0", "fin_mode1"]
+    assert reached == ["pull_f32", "pull_mode1", "pull_mode2", "pull_mode3", "fin_mode0", "fin_mode1"]
 
 
 @pytest.mark.parametrize("bad", [INF, NAN])
