@@ -18,6 +18,11 @@ deterministic and lazy, labels item-derived — plumbing, not learnable data.
 Augmentations (data.py:258-276) are restated on numpy arrays: the reference
 applies torch ops to numpy items and crashes, here they accept
 either and return the input's type.
+
+``raw()`` on each dataset returns the stored items as arrays, and
+``device_loader(dataset, batch_size)`` puts them on the device behind a
+``dgx.loader.DeviceLoader`` that applies the partition's shuffle and
+augmentation there, one launch per batch; ``__getitem__`` is untouched by both.
 """
 import glob
 import math
@@ -113,6 +118,19 @@ def _synthetic_cloud(seed, n, channels=3):
     return (2.0 * synth.uniform(seed, (n, channels)) - 1.0).astype(np.float32)
 
 
+def _synthetic_clouds(seeds, n, channels=3):
+    """``_synthetic_cloud`` of every seed, stacked, 512 clouds at a time."""
+    seeds = np.asarray(seeds, np.int64)
+    out = np.empty((len(seeds), n, channels), np.float32)
+    for a in range(0, len(seeds), 512):
+        out[a:a + 512] = 2.0 * synth.uniform_many(seeds[a:a + 512], (n, channels)) - 1.0
+    return out
+
+
+def _item_ids(n, items):
+    return np.arange(n) if items is None else np.arange(n)[items].reshape(-1)
+
+
 def _as_numpy(pc):
     return pc.numpy() if isinstance(pc, torch.Tensor) else pc
 
@@ -170,6 +188,15 @@ class ModelNet40(Dataset):
             np.random.shuffle(pc)
         return pc, label
 
+    def raw(self, items=None):
+        """The stored items without augmentation or shuffle, for
+        ``device_loader``: (points (n, 2048, 3) float32, label (n,) int64,
+        None). ``items``: indices (default: all)."""
+        ids = _item_ids(self.n, items)
+        if self.SYNTHETIC:
+            return _synthetic_clouds(1000003 * (1 + (self.partition == "test")) + ids, 2048), ids % 40, None
+        return self.data[ids], self.label[ids].reshape(-1), None
+
     def __len__(self):
         return self.n
 
@@ -220,6 +247,18 @@ class ShapeNetPart(Dataset):
             pc, seg = pc[perm], seg[perm]
         return pc, np.array([cat], np.int64), seg
 
+    def raw(self, items=None):
+        """The stored items without the point shuffle, for ``device_loader``:
+        (points (n, 2048, 3) float32, label (n,) int64, seg (n, 2048) int64).
+        ``items``: indices (default: all)."""
+        ids = self.items[_item_ids(len(self.items), items)]
+        cat = self.labels[ids]
+        if self.SYNTHETIC:
+            start, num = np.asarray(self.index_start)[cat], np.asarray(self.seg_num)[cat]
+            return (_synthetic_clouds(2000003 + ids, 2048), cat,
+                    (start[:, None] + np.arange(2048)[None, :] % num[:, None]).astype(np.int64))
+        return self.data[ids], cat, self.seg[ids]
+
     def __len__(self):
         return len(self.items)
 
@@ -267,6 +306,16 @@ class ShapeNetPart_Augmented(Dataset):
 
     def __len__(self):
         return len(self.data)
+
+    def raw(self, items=None):
+        """The stored items without augmentation, for ``device_loader``:
+        (points (n, P, 3) float32, label (n,) int64, seg (n, P) int64).
+        ``items``: indices (default: all)."""
+        if self.SYNTHETIC:
+            return self.data.raw(items)
+        ids = _item_ids(len(self.data), items)
+        pc, label, seg = (np.asarray(t)[ids] for t in self.data.tensors)
+        return pc.astype(np.float32), label.reshape(len(ids)).astype(np.int64), seg.astype(np.int64)
 
     def __getitem__(self, index):
         pc, label, seg = self.data[index]
@@ -323,5 +372,59 @@ class S3DIS(Dataset):
             block, seg = block[perm], seg[perm]
         return block.astype(np.float32), torch.LongTensor(np.asarray(seg, np.int64))
 
+    def raw(self, items=None):
+        """The stored blocks without the point shuffle, for ``device_loader``:
+        (points (n, 4096, 9) float32, None, seg (n, 4096) int64). ``items``:
+        indices (default: all)."""
+        ids = _item_ids(self.n, items)
+        if self.SYNTHETIC:
+            out = np.empty((len(ids), 4096, 9), np.float32)
+            for a in range(0, len(ids), 256):
+                u = synth.uniform_many(3000003 + ids[a:a + 256], (4096, 9))   # synth.s3dis_blocks of each seed
+                u[..., 0:2] -= np.float32(0.5)
+                u[..., 2] *= np.float32(3.0)
+                out[a:a + 256] = u
+            return out, None, (np.arange(4096)[None, :] * 7 + ids[:, None]) % 13
+        return self.data[ids].astype(np.float32), None, self.seg[ids].astype(np.int64)
+
     def __len__(self):
         return self.n
+
+
+def device_loader(dataset, batch_size, items=None, device="cuda", **kwargs):
+    """A ``dgx.loader.DeviceLoader`` over ``dataset.raw(items)`` with the
+    policy of the dataset's own ``__getitem__`` for its partition:
+
+      ModelNet40 train              translate + point shuffle
+      ShapeNetPart trainval         point shuffle
+      ShapeNetPart_Augmented train  translate / jitter / rotate, random order and switches
+      S3DIS train                   point shuffle (9 channels)
+      other partitions              neither
+
+    Training partitions sample in shuffled order, the others in file order
+    (``DistributedSampler`` either way). The ShapeNetPart classes yield
+    ``(data, onehot (B, 16), seg - seg_start_index, label)``, the others
+    ``(data, label, seg)``. ``kwargs`` go to the ``DeviceLoader`` and override
+    the policy."""
+    from dgx.loader import DeviceLoader
+    points, label, seg = dataset.raw(items)
+    train = dataset.partition in ("train", "trainval")
+    policy = {"shuffle": train, "shuffle_points": False, "augment": "none"}
+    if isinstance(dataset, ModelNet40):
+        policy.update(num_points=dataset.num_points)
+        if dataset.partition == "train":
+            policy.update(shuffle_points=True, augment="translate")
+    elif isinstance(dataset, ShapeNetPart):
+        policy.update(num_points=dataset.num_points, shuffle_points=dataset.partition == "trainval",
+                      seg_start_index=dataset.seg_start_index, num_categories=len(dataset.seg_num))
+    elif isinstance(dataset, ShapeNetPart_Augmented):
+        policy.update(augment="random3" if dataset.partition == "train" else "none",
+                      num_categories=len(ShapeNetPart.seg_num))
+    elif isinstance(dataset, S3DIS):
+        policy.update(num_points=dataset.num_points, shuffle_points=dataset.partition == "train")
+    else:
+        raise TypeError(f"device_loader: {type(dataset).__name__} is none of this module's datasets")
+    policy.update(kwargs)
+    as_t = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a).astype(dt, copy=False))
+    return DeviceLoader(as_t(points, np.float32), as_t(seg, np.int32), as_t(label, np.int32), batch_size=batch_size,
+                        device=device, **policy)

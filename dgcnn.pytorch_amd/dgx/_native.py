@@ -148,6 +148,9 @@ _SIGS = {
     "dgx_seg_metrics_max_classes": [],
     "dgx_seg_metrics_update": [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i32,
                                _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "dgx_batch_max_points": [],
+    "dgx_batch_assemble": [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i32, _i64, _i64, _i32, ctypes.c_uint64,
+                           ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "dgx_version": ctypes.c_char_p,

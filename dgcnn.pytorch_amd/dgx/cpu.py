@@ -307,3 +307,166 @@ def attention(q, k, v, heads, dropout_p=0.0, scale=None):
     o = F.scaled_dot_product_attention(qh, kh, vh, dropout_p=dropout_p, scale=scale)
     return o.transpose(1, 2).reshape(B, Nq, E)
 
+
+
+# ---- dgx_batch_assemble (include/dgx.h) on the host: the same Philox4x32-10 words, the same stable argsort, the
+# same fp32 operation sequence (numpy rounds every multiply and add on its own). The libm-dependent draws (theta,
+# cos, sin, noise) are evaluated in fp64 and rounded once, so they may differ from the device's in the last bits.
+BATCH_SHUFFLE, BATCH_TRANSLATE, BATCH_RANDOM3, BATCH_FORCE = 1, 1 << 1, 2 << 1, 8
+BATCH_ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))   # 0 translate, 1 jitter, 2 rotate
+_B_CURSOR, _B_EPOCH, _B_INVALID, _B_OVERRUN, _B_BATCHES = 0, 1, 2, 3, 4
+_U32 = np.uint64(0xFFFFFFFF)
+_f32 = np.float32
+
+
+def batch_flags(shuffle_points, augment, order=None, switches=None):
+    """The flags word of dgx_batch_assemble. ``order`` (0..5) and ``switches``
+    (bit a: augmentation a on) force the random3 draw (tests only)."""
+    aug = {"none": 0, "translate": BATCH_TRANSLATE, "random3": BATCH_RANDOM3}
+    if augment not in aug:
+        raise ValueError(f"dgx: augment is one of {sorted(aug)}, got {augment!r}")
+    flags = (BATCH_SHUFFLE if shuffle_points else 0) | aug[augment]
+    if order is not None or switches is not None:
+        if augment != "random3" or not 0 <= int(order or 0) <= 5 or not 0 <= int(switches or 0) <= 7:
+            raise ValueError("dgx: a forced draw needs augment='random3', order 0..5 and switches 0..7")
+        flags |= BATCH_FORCE | int(order or 0) << 4 | int(switches or 0) << 7
+    return flags
+
+
+def philox4x32(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11) on broadcastable integer arrays:
+    the four output words as uint32 arrays."""
+    c0, c1, c2, c3 = (np.asarray(v).astype(np.uint64) & _U32 for v in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = np.uint64(int(k0) & 0xFFFFFFFF), np.uint64(int(k1) & 0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _U32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _U32, (k1 + np.uint64(0xBB67AE85)) & _U32
+    return tuple(v.astype(np.uint32) for v in (c0, c1, c2, c3))
+
+
+def _unit(w):      # U(w): [0, 1), exact in fp32
+    return (np.asarray(w, np.uint32) >> np.uint32(8)).astype(_f32) * _f32(2.0 ** -24)
+
+
+def _normal64(wr, wa, sin=False):
+    """Box-Muller in fp64 from the words' exact fp32 uniforms: R(wr) cos / sin(2 pi U(wa))."""
+    u1 = ((np.asarray(wr, np.uint32) >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    ang = 2.0 * np.pi * _unit(wa).astype(np.float64)
+    return np.sqrt(-2.0 * np.log(u1)) * (np.sin(ang) if sin else np.cos(ang))
+
+
+def batch_words(item, epoch, seed, stream, block):
+    return philox4x32(np.uint32(int(item) & 0xFFFFFFFF), np.uint32(int(epoch) & 0xFFFFFFFF), stream, block,
+                      int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
+
+
+def batch_draws64(item, epoch, seed, n_points):
+    """The libm-dependent draws of one cloud in fp64 from the same integer
+    words: (theta, noise (n_points, 3) before rounding to fp32)."""
+    w = batch_words(item, epoch, seed, 0, 0)
+    theta = 2.0 * np.pi * float(_normal64(w[2], w[3]))
+    g = batch_words(item, epoch, seed, 2, np.arange(n_points, dtype=np.uint32))
+    z = np.stack([_normal64(g[0], g[1]), _normal64(g[0], g[1], sin=True), _normal64(g[2], g[3])], axis=1)
+    return theta, np.clip(0.01 * z, -0.02, 0.02)
+
+
+def batch_params(item, epoch, seed, flags):
+    """One cloud's stream-0 draws: the (16,) fp32 row that dgx_batch_assemble
+    exports as ``params``."""
+    q = np.zeros(16, _f32)
+    aug = (flags >> 1) & 3
+    q[4:7] = 1.0
+    q[11] = 1.0
+    if aug:
+        w0 = batch_words(item, epoch, seed, 0, 0)
+        order, sw = (int(w0[0]) % 6, int(w0[1]) & 7) if aug == 2 else (0, 1)
+        if flags & BATCH_FORCE:
+            order, sw = min((flags >> 4) & 7, 5), (flags >> 7) & 7
+        w1, w2 = batch_words(item, epoch, seed, 0, 1), batch_words(item, epoch, seed, 0, 2)
+        q[0] = order
+        q[1:4] = [(sw >> a) & 1 for a in range(3)]
+        q[4:7] = _f32(2.0) / _f32(3.0) + _unit(np.stack(w1[:3])) * (_f32(5.0) / _f32(6.0))
+        q[7:10] = _f32(-0.2) + _unit(np.stack(w2[:3])) * _f32(0.4)
+        q[10] = _f32(2.0 * np.pi) * _f32(_normal64(w0[2], w0[3]))
+        q[11], q[12] = np.cos(np.float64(q[10])), np.sin(np.float64(q[10]))
+    q[13:15] = np.array([int(item) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF], np.uint32).view(_f32)
+    return q
+
+
+def batch_perm(item, epoch, seed, n_points):
+    """The shuffle of one cloud's first ``n_points`` points: a stable argsort
+    of the stream-1 keys (the order of the distinct words (key << 32) | j)."""
+    j = np.arange(n_points, dtype=np.uint32)
+    words = np.stack(batch_words(item, epoch, seed, 1, j >> np.uint32(2)))   # (4, n): word r of block j / 4
+    return np.argsort(words[j & np.uint32(3), j], kind="stable").astype(np.int32)
+
+
+def batch_apply(pc, params, noise):
+    """The augmentations of one cloud ``pc`` (N, 3) fp32 in the order and with
+    the switches of its ``params`` row, each operation rounded to fp32 on its
+    own: translate is data.translate_pointcloud's ``pc * scale + shift``."""
+    pc = np.array(pc, _f32)
+    scale, shift, c, s = params[4:7], params[7:10], params[11], params[12]
+    for op in BATCH_ORDERS[int(params[0])]:
+        if not params[1 + op]:
+            continue
+        if op == 0:
+            pc = pc * scale + shift
+        elif op == 1:
+            pc = pc + noise
+        else:
+            x, z = pc[:, 0].copy(), pc[:, 2].copy()
+            pc[:, 0] = x * c + z * s
+            pc[:, 2] = -(x * s) + z * c
+    return pc
+
+
+def batch_assemble(points, seg, label, order, state, B, N, seg_start, ncat, seed, flags, out, seg_out=None,
+                   label_out=None, onehot=None, perm=None, params=None, noise=None):
+    """dgx_batch_assemble on host tensors, outputs and ``state`` in place."""
+    pts = points.numpy()
+    n_items, n_epoch = pts.shape[0], order.numel()
+    cursor, epoch = int(state[_B_CURSOR]), int(state[_B_EPOCH])
+    aug = (flags >> 1) & 3
+    for b in range(B):
+        slot = cursor + b
+        if cursor < 0 or slot >= n_epoch:
+            state[_B_OVERRUN] += 1
+            continue
+        item = int(order[slot])
+        ok = 0 <= item < n_items
+        lab = int(label[item]) if ok and label is not None else 0
+        if ok and ncat > 0 and not 0 <= lab < ncat:
+            ok = False
+        if not ok:
+            state[_B_INVALID] += 1
+            for t in (out, seg_out, label_out, onehot, perm, params, noise):
+                if t is not None:
+                    t[b].zero_()
+            continue
+        src = batch_perm(item, epoch, seed, N) if flags & BATCH_SHUFFLE else np.arange(N, dtype=np.int32)
+        pc = pts[item, src.astype(np.int64)]
+        q = batch_params(item, epoch, seed, flags)
+        if aug:
+            nz = None
+            if noise is not None or q[2]:
+                nz = batch_draws64(item, epoch, seed, N)[1].astype(_f32)
+            pc = batch_apply(pc, q, nz)
+            if noise is not None:
+                noise[b] = torch.from_numpy(nz)
+        out[b] = torch.from_numpy(np.ascontiguousarray(pc.T))
+        if seg_out is not None:
+            seg_out[b] = torch.from_numpy(seg.numpy()[item, src.astype(np.int64)].astype(np.int64) - int(seg_start))
+        if label_out is not None:
+            label_out[b] = lab
+        if onehot is not None:
+            onehot[b].zero_()
+            onehot[b, lab] = 1.0
+        if perm is not None:
+            perm[b] = torch.from_numpy(src)
+        if params is not None:
+            params[b] = torch.from_numpy(q)
+    if 0 <= cursor < n_epoch:
+        state[_B_CURSOR] = min(cursor + B, n_epoch)
+    state[_B_BATCHES] += 1

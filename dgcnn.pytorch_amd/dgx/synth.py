@@ -27,6 +27,19 @@ def uniform(seed, shape):
     return u.reshape(shape)
 
 
+def uniform_many(seeds, shape):
+    """``uniform(seed, shape)`` of every seed, stacked: (len(seeds),) + shape."""
+    n = int(np.prod(shape))
+    seeds = np.asarray(seeds, np.uint64).reshape(-1, 1)
+    with np.errstate(over="ignore"):
+        z = seeds + np.arange(1, n + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+    return u.reshape((seeds.shape[0],) + tuple(shape))
+
+
 def cube_clouds(B, N, seed=0):
     """(B,N,3) float32 in [-1,1): the cls/partseg workload."""
     return (uniform(seed, (B, N, 3)) * np.float32(2.0) - np.float32(1.0)).astype(np.float32)

@@ -773,6 +773,89 @@ int dgx_seg_metrics_update(const void* scores, int dtype, int64_t B, int64_t C, 
                            int32_t* iu, int32_t* nparts, int64_t capacity, int max_parts, int64_t* state,
                            const float* loss, float* loss_sum, void* stream);
 
+/* ---- batches assembled on the device from a device-resident dataset (the
+ * reference's input side: ShapeNetPart_Augmented.__getitem__ data.py:353-364,
+ * the default collate, the one-hot loop main_partseg_dist.py:241-244, three
+ * H2D copies and permute(0, 2, 1).contiguous()). One call builds one batch in
+ * one launch, one workgroup per output cloud, and never touches the host.
+ *
+ * Dataset: points fp32 [n_items][P][C]; seg int32 [n_items][P] (NULL: none);
+ * label int32 [n_items] (NULL: none). order: this rank's item ids of the epoch,
+ * int32 [n_epoch]. state: DGX_BATCH_STATE_WORDS int64 words
+ *   [0] cursor   clouds of `order` served so far; workgroup b of a call serves
+ *                slot cursor + b; the call advances it to min(cursor + B, n_epoch)
+ *   [1] epoch    the caller's; its low 32 bits enter the random counter
+ *   [2] invalid  clouds whose item id is outside [0, n_items) or (ncat > 0)
+ *                whose label is outside [0, ncat): all their outputs are zeros
+ *   [3] overrun  workgroups whose slot is >= n_epoch: they write nothing
+ *   [4] batches  += 1 per call
+ *   [5] ticket   0 between calls (the kernel's own)
+ * Calls on one state must be ordered (one stream, or a linear graph).
+ *
+ * Cloud b of the call, item = order[cursor + b], with src(n) = perm[n] if
+ * DGX_BATCH_SHUFFLE else n, for n < N <= P (the first N points are taken
+ * before the shuffle):
+ *   out      fp32  [B][C][N]  out[b][c][n] = aug(points[item][src(n)])[c]
+ *   seg_out  int64 [B][N]     seg[item][src(n)] - seg_start   (with seg)
+ *   label_out int64 [B]       label[item]                     (with label)
+ *   onehot   fp32  [B][ncat]  1 at label[item], 0 elsewhere   (ncat > 0; needs label)
+ * Debug outputs (NULL in normal use):
+ *   perm     int32 [B][N]     src(n)
+ *   params   fp32  [B][16]    [0] order index o, [1..3] switches of translate,
+ *                             jitter, rotate (0 / 1), [4..6] scale, [7..9] shift,
+ *                             [10] theta, [11] cos, [12] sin, [13] the bits of the
+ *                             int32 item id, [14] the bits of the epoch's low word,
+ *                             [15] 0
+ *   noise    fp32  [B][N][3]  the jitter draw of output point n (drawn whether
+ *                             or not jitter is on when this output is asked for)
+ *
+ * Random numbers: Philox4x32-10 (Salmon et al., SC'11; multipliers D2511F53 /
+ * CD9E8D57, key increments 9E3779B9 / BB67AE85). Key = (seed low word, seed
+ * high word). Counter = (item id, epoch low word, stream, block); w0..w3 are
+ * the four output words in order. A cloud's draws depend on (seed, epoch,
+ * item) only. With U(w) = (w >> 8) * 2^-24 in [0, 1), U1(w) = ((w >> 8) + 1) *
+ * 2^-24 in (0, 1], R(w) = sqrtf(-2 logf(U1(w))), all in fp32:
+ *   stream 0  block 0: o = w0 % 6; switch of augmentation a = bit a of w1 (a = 0
+ *               translate, 1 jitter, 2 rotate); theta = (float)(2 pi) * (R(w2) *
+ *               cospif(2 U(w3))) — normal, not uniform (data.py:272); cos =
+ *               cosf(theta), sin = sinf(theta)
+ *             block 1: scale[c] = 2/3 + U(w_c) * 5/6, c = 0..2 (fp32 constants,
+ *               one rounding per operation)
+ *             block 2: shift[c] = -0.2 + U(w_c) * 0.4
+ *   stream 1  block q: w_r is the shuffle key of point 4 q + r. perm is the
+ *             ascending order of the 64-bit words (key << 32) | j, j < N: a stable
+ *             argsort of the keys
+ *   stream 2  block n (output point n): z0 = R(w0) cospif(2 U(w1)), z1 = R(w0)
+ *             sinpif(2 U(w1)), z2 = R(w2) cospif(2 U(w3)); noise[n][c] =
+ *             clamp(0.01f * z_c, -0.02f, 0.02f)
+ * Order o applies the augmentations whose switch is on in the sequence
+ *   0: T J R   1: T R J   2: J T R   3: J R T   4: R T J   5: R J T
+ * (data.py:357-362 shuffles the three functions and draws three switches), with
+ * every multiply and add rounded on its own (no FMA):
+ *   T  p[c] = p[c] * scale[c] + shift[c]
+ *   J  p[c] = p[c] + noise[n][c]
+ *   R  x' = x * cos + z * sin;  z' = -(x * sin) + z * cos   (x = p[0], z = p[2])
+ * so the host reproduces `out` bit for bit from params, noise and perm. The
+ * dataset is never written.
+ *
+ * flags: DGX_BATCH_SHUFFLE | one of DGX_BATCH_AUG_NONE / _TRANSLATE (T always on,
+ * nothing else: ModelNet40 train) / _RANDOM3 (the draw above). Tests may force
+ * the draw: DGX_BATCH_FORCE | o << 4 | switches << 7. Augmentation needs C == 3
+ * (else DGX_EINVAL). The shuffle sorts in LDS, 8 bytes per point of the next
+ * power of two: N <= dgx_batch_max_points() (4096: 32 KiB), else
+ * DGX_EUNSUPPORTED; without it any N is taken and no LDS is used. */
+#define DGX_BATCH_STATE_WORDS 8
+#define DGX_BATCH_SHUFFLE 1u
+#define DGX_BATCH_AUG_NONE (0u << 1)
+#define DGX_BATCH_AUG_TRANSLATE (1u << 1)
+#define DGX_BATCH_AUG_RANDOM3 (2u << 1)
+#define DGX_BATCH_FORCE 8u
+int dgx_batch_max_points(void);
+int dgx_batch_assemble(const float* points, const int32_t* seg, const int32_t* label, int64_t n_items, int64_t P,
+                       int C, const int32_t* order, int64_t n_epoch, int64_t* state, int B, int64_t N,
+                       int64_t seg_start, int ncat, uint64_t seed, uint32_t flags, float* out, int64_t* seg_out,
+                       int64_t* label_out, float* onehot, int32_t* perm, float* params, float* noise, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
