@@ -1431,6 +1431,26 @@ inline int scatter_parts(int B, int slices, int N, int cs, bool packed) {
     return parts;
 }
 
+// lanes per point (the kernel's TPP) of the packed dz|slot words at 8-channel
+// slices: 2 for parts of more than 128 points, up to SCATTER_SMALL_TPP while a
+// part's points x lanes fit the block (few-cloud shards, whose grids are
+// widened by point parts); every other form keeps one lane per point.
+// cfg2 (r09o, mean of the step's 4 bf16 launches): 1 lane 56.2 us, 2 lanes
+// 52.5, 4 lanes 57.8; 4-cloud shard (r09m): 1 lane 20.3, 4 lanes 14.1, 8 lanes
+// 14.4 us
+#ifndef SCATTER_SMALL_TPP
+#define SCATTER_SMALL_TPP 4
+#endif
+inline int scatter_lanes(int N, int parts, int cs, bool packed) {
+    const int per_pts = (N + parts - 1) / parts;
+    int tpp = 2;
+    while (tpp < SCATTER_SMALL_TPP && per_pts * 2 * tpp <= EC_THREADS) tpp *= 2;
+#ifdef SCATTER_FORCE_TPP   // (A/B builds) the same lanes per point at any part size
+    tpp = SCATTER_FORCE_TPP;
+#endif
+    return tpp > 1 && cs == 8 && packed ? tpp : 1;
+}
+
 // launch_scatter's own shape test, without a launch
 inline bool scatter_fits(int B, int N, int Co, bool packed) {
     if (N < 1 || N > 65535) return false;
@@ -1478,21 +1498,8 @@ int launch_scatter(const float* PQ, int ldpq, const int32_t* rowptr, const int32
         }                                                                   \
         break;
     // packed dz|slot words at 8-channel slices: TPP lanes per point
-    // (edge_bwd_scatter_kernel): 2 for parts of 256+ points, up to
-    // SCATTER_SMALL_TPP while a part's points x lanes fit the block (few-cloud
-    // shards, whose grids are widened by point parts). cfg2 (r09o, mean of the
-    // step's 4 bf16 launches): 1 lane 56.2 us, 2 lanes 52.5, 4 lanes 57.8;
-    // 4-cloud shard (r09m): 1 lane 20.3, 4 lanes 14.1, 8 lanes 14.4 us
-#ifndef SCATTER_SMALL_TPP
-#define SCATTER_SMALL_TPP 4
-#endif
-    const int per_pts = (N + parts - 1) / parts;
-    int tpp = 2;
-    while (tpp < SCATTER_SMALL_TPP && per_pts * 2 * tpp <= EC_THREADS) tpp *= 2;
-#ifdef SCATTER_FORCE_TPP   // (A/B builds) the same lanes per point at any part size
-    tpp = SCATTER_FORCE_TPP;
-#endif
-    if (tpp > 1 && cs == 8 && packed) {
+    const int tpp = scatter_lanes(N, parts, cs, packed);
+    if (tpp > 1) {
 #define DGX_SCATTER_TPP(O16, SP)                                             \
     if (tpp >= 8) DGX_SCATTER_LAUNCH_T(8, O16, true, SP, 8);                 \
     else if (tpp == 4) DGX_SCATTER_LAUNCH_T(8, O16, true, SP, 4);            \
@@ -1519,6 +1526,19 @@ int launch_scatter(const float* PQ, int ldpq, const int32_t* rowptr, const int32
 
 int dgx_edge_bwd_scatter_fits(int B, int N, int Co, int packed) {
     return B >= 1 && Co >= 1 && scatter_fits(B, N, Co, packed != 0) ? 1 : 0;
+}
+
+int dgx_edge_bwd_scatter_geometry(int B, int N, int Co, int packed, int* cs, int* parts, int* tpp,
+                                  int64_t* lds_bytes) {
+    if (!dgx_edge_bwd_scatter_fits(B, N, Co, packed)) return DGX_EUNSUPPORTED;
+    const bool pk = packed != 0;
+    const int c = scatter_slice_channels(N, pk);
+    const int p = scatter_parts(B, (Co + c - 1) / c, N, c, pk);
+    if (cs) *cs = c;
+    if (parts) *parts = p;
+    if (tpp) *tpp = scatter_lanes(N, p, c, pk);
+    if (lds_bytes) *lds_bytes = (int64_t)scatter_lds_bytes(N, c, p, pk);
+    return DGX_OK;
 }
 
 int dgx_edge_bwd_scatter_max_n(int B, int Co, int packed) {

@@ -259,7 +259,13 @@ int dgx_graph_reverse_multi(int n, const int32_t* const* idx, int B, int N, int 
                             int32_t* const* rowptr, int32_t* const* edges, void* stream);
 /* dPQ output (out_bf16): 0 fp32, 1 bf16, 2 split bf16 planes — hi = bf16(v)
  * at dPQ, lo = bf16(v - hi) at dPQ + B*N*2Co elements — or 3: (hi, lo, hi),
- * hi again at dPQ + 2*B*N*2Co (the fp32 mode's 3-pass GEMM operands). */
+ * hi again at dPQ + 2*B*N*2Co (the fp32 mode's 3-pass GEMM operands).
+ * Alignment (this entry, _fin_f32 and _packed_f32; not checked): the bases of
+ * PQ, dz, sumP and dPQ are 16-byte aligned — with Co % 4 == 0 (and, for PQ,
+ * ldpq % 4 == 0) rows are read and written in 16-byte (bf16 output: 8-byte)
+ * accesses at multiples of 4 channels from those bases. arg is 8-byte
+ * aligned (rows are read cs <= 8 bytes at a time when Co % cs == 0); rowptr
+ * and edges need their element alignment only. */
 int dgx_edge_bwd_scatter_f32(const float* PQ, int ldpq, const int32_t* rowptr,
                              const int32_t* edges, const float* dz,
                              const uint8_t* arg, const float* sumP, int B, int N,
@@ -274,6 +280,14 @@ int dgx_edge_bwd_scatter_f32(const float* PQ, int ldpq, const int32_t* rowptr,
 int dgx_edge_bwd_scatter_max_n(int B, int Co, int packed);
 /* Host-only, O(1): 1 when the pull scatters take this shape, else 0. */
 int dgx_edge_bwd_scatter_fits(int B, int N, int Co, int packed);
+/* Host-only: the launch form the pull scatters take for this shape, from the
+ * launcher's own rules: cs = channels per slice (8, 4, 2 or 1), parts = point
+ * parts per cloud, tpp = lanes per point (2 or 4 with packed words at cs = 8,
+ * else 1), lds_bytes = the workgroup's dynamic LDS. Any output may be NULL.
+ * DGX_EUNSUPPORTED (nothing written) exactly where dgx_edge_bwd_scatter_fits
+ * is 0. */
+int dgx_edge_bwd_scatter_geometry(int B, int N, int Co, int packed, int* cs, int* parts,
+                                  int* tpp, int64_t* lds_bytes);
 /* dgx_bn_bwd_finalize_f32 + dgx_edge_bwd_scatter_f32 in ONE launch: every
  * workgroup reduces the dz pass's partial rows (nrows x 2 x Co) for its own
  * channels in a fixed order (fp64) and the channel slice's first workgroup

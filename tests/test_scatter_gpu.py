@@ -14,6 +14,8 @@ dz of its in-edges from the cloud's LDS slices, so:
 * the largest cloud runs, one more point is refused before any launch, and the
   training forward names that limit."""
 
+import ctypes
+
 import pytest
 import torch
 
@@ -154,13 +156,14 @@ def test_pull_split_planes_output(cuda, packed, B, N, k, Co, mode):
 BW_LDS_BYTES = 72 * 1024   # csrc/edgeconv.hip: the Q | dz | slot slices of two workgroups per CU
 
 
-def _scatter_cs(N, packed):
-    """launch_scatter's slice width: 9 bytes per (point, channel) with slot bytes,
+def _scatter_cs(N, packed, B=1, Co=8):
+    """launch_scatter's slice width, from the launcher's own rules
+    (dgx_edge_bwd_scatter_geometry): 9 bytes per (point, channel) with slot bytes,
     8 with packed dz|slot words, halved from 8 channels until the slice fits."""
-    cs = 8
-    while cs > 1 and (8 if packed else 9) * N * cs > BW_LDS_BYTES:
-        cs //= 2
-    return cs
+    cs = ctypes.c_int(-1)
+    nat.check(nat.lib().dgx_edge_bwd_scatter_geometry(B, N, Co, int(packed), ctypes.byref(cs), None, None, None),
+              "scatter geometry")
+    return cs.value
 
 
 # one ragged N per geometry (the same for both dz forms): 8 / 4 / 2 / 1 channels
