@@ -61,9 +61,36 @@ __device__ __forceinline__ float to_f(bf16 v) { return (float)v; }
 // Blocks b and b+8 share an XCD (MI355X_MICROARCH.md); give each XCD a
 // contiguous range of logical tiles (bijective for any grid size) so the blocks
 // that share an A row panel share that XCD's L2.
-__device__ __forceinline__ int xcd_remap(int id, int n) {
+__host__ __device__ __forceinline__ int xcd_remap(int id, int n) {
     const int q = n >> 3, r = n & 7, x = id & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (id >> 3);
+}
+
+// Logical id L of an nI x nJ tile grid -> (ti, tj), in groups of two row tiles:
+// the 4 consecutive tiles an XCD takes (xcd_remap) form a 2 x 2 square, so each
+// A row panel and each B column panel of a K-chunk is fetched by half as many
+// XCDs as in row-major order (which shares A panels but sends every B panel to
+// all eight)
+__host__ __device__ __forceinline__ void tile_2row(int L, int nI, int nJ, int& ti, int& tj) {
+    const int gsz = 2 * nJ, grp = L / gsz, first = grp * 2, gm = nI - first < 2 ? nI - first : 2, r = L - grp * gsz;
+    ti = first + r % gm;
+    tj = r / gm;
+}
+
+// Workgroup map of the split-K TN launches (flat grid of nI * nJ * slabs):
+// chunk-major. xcd_remap hands each XCD a contiguous range of logical ids and a
+// logical id is (chunk, tile) with the tile fastest, so an XCD runs whole
+// K-chunks: all output tiles of a chunk share one L2 and every operand byte of
+// the chunk is filled into it once. (With tiles on grid.x and chunks on grid.y
+// each XCD kept the same few tiles through every chunk and filled their A and B
+// panels again per chunk: 2.7 x the unique bytes for conv5's dW.) Tiles of a
+// chunk keep the 2-row grouping. A bijection for any (nI, nJ, slabs).
+__host__ __device__ __forceinline__ void tn_chunk_major(int id, int nI, int nJ, int slabs, int& ti, int& tj,
+                                                        int& chunk) {
+    const int tiles = nI * nJ;
+    const int L = xcd_remap(id, tiles * slabs);
+    chunk = L / tiles;
+    tile_2row(L - chunk * tiles, nI, nJ, ti, tj);
 }
 
 // Stages a TILE x BK slab of op(i,k), i in [i0, i0+TILE) clipped to `rows`,
@@ -417,9 +444,11 @@ __global__ __launch_bounds__(SR_E * SR_G) void slab_reduce_multi_kernel(SlabJobs
 // Both operands bf16 in HBM, either both k-contiguous ("NT": C = A B^T, the
 // forward PQ / conv5 and the input gradients with pre-transposed weights) or
 // both i-contiguous ("TN": C = A^T B, the weight gradients, K = M rows split
-// over workgroups). 128 x BN x 64 tiles, 4 waves (2 x 2), two LDS stages: the
+// over workgroups). 128 x BN x 64 tiles, 4 waves (2 x 2). NT: two LDS stages, the
 // next stage's DMA is issued before the current stage's MFMAs and retired by
 // one vmcnt(0) + barrier per stage (cdna_hip_programming.md §5.5 T3+T4, 2-phase).
+// TN: a ring of tn_depth stages with a counted vmcnt and a raw s_barrier per
+// stage, on a flat chunk-major grid (tn_chunk_major); see the kernel's main loop.
 // The LDS destination of a DMA is lane-linear, so the bank swizzles are
 // applied to each lane's SOURCE address:
 //   NT image [row][64 k] (128-B rows): 16-B chunk c of row r at c ^ (r & 7) —
@@ -481,19 +510,52 @@ __device__ __forceinline__ bf16x8 frag_nt(const bf16* img, int row, int chunk) {
     return *reinterpret_cast<const bf16x8*>(img + row * 64 + ((chunk ^ (row & 7)) << 3));
 }
 
+// The TN fragment reads are inline assembly: behind the ds_read_tr16_b64 builtin
+// hipcc waits for vmcnt(0) before every read while an LDS-DMA is in flight (it
+// cannot tell the read from the DMA's destination), which serialises the next
+// stage's loads with this stage's MFMAs. The compiler does not count these reads
+// either, so a K sub-step issues them (tn_read), waits for lgkmcnt(0) and only
+// then hands the registers to the MFMAs (tn_landed).
+//
+// Byte offset, within a [k][TILE] stage image, of the lane's address for the
+// k-rows {4g + q} of columns [col0, col0 + 16); rows + 16 and + 32 keep the
+// swizzle (tn_swz takes row bits 0..2), so they are constant byte offsets.
 template <int TILE>
-__device__ __forceinline__ bf16x8 frag_tn(const bf16* img, int s, int col0, int lane) {
+__device__ __forceinline__ uint32_t tn_frag_off(int col0, int lane) {
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
     const int chunk = (col0 >> 3) + (p >> 1);
-    const int r1 = 32 * s + 4 * g + q, r2 = r1 + 16;
-    const bf16* a1 = img + r1 * TILE + ((chunk ^ tn_swz(r1, TILE)) << 3) + 4 * (p & 1);
-    const bf16* a2 = img + r2 * TILE + ((chunk ^ tn_swz(r2, TILE)) << 3) + 4 * (p & 1);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)const_cast<bf16*>(a1));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)const_cast<bf16*>(a2));
+    const int r1 = 4 * g + q;
+    return 2u * (uint32_t)(r1 * TILE + ((chunk ^ tn_swz(r1, TILE)) << 3) + 4 * (p & 1));
+}
+// k-rows {4g + q} (lo) and {16 + 4g + q} (hi) of the 32-deep sub-step at `addr`
+template <int TILE>
+__device__ __forceinline__ void tn_read(uint32_t addr, s16x4& lo, s16x4& hi) {
+    asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
+                 : "=&v"(lo), "=&v"(hi)
+                 : "v"(addr), "n"(16 * TILE * 2)
+                 : "memory");
+}
+// after the s_waitcnt that follows the reads: the fragment, usable from here on
+__device__ __forceinline__ bf16x8 tn_landed(s16x4 lo, s16x4 hi) {
+    asm volatile("" : "+v"(lo), "+v"(hi));
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
+}
+
+// LDS stages of a TN tile: the deepest ring (3) that leaves room for two
+// workgroups per CU (2 x 80 KiB), else 2. 128 x 128 tiles (32 KiB stages) keep 2:
+// a third stage costs the second workgroup, which is worth more.
+constexpr int tn_depth(int bm, int bn) { return 3 * (bm + bn) * G2_BK * 2 <= 80 * 1024 ? 3 : 2; }
+
+// s_waitcnt vmcnt(n * P): at most n stages of P loads each stay in flight
+// (n <= 0 drains the queue); n <= MAXN
+template <int P, int MAXN>
+__device__ __forceinline__ void wait_dma(int n) {
+    static_assert(MAXN <= 2 && MAXN * P <= 63, "vmcnt is a 6-bit counter");
+    if (MAXN >= 2 && n >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P) : "memory");
+    else if (MAXN >= 1 && n == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 template <bool TN, int BM, int BN, int EPI>
@@ -506,26 +568,23 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_lds_kernel(
     constexpr int WM = 4 / WN;
     constexpr int TM = BM / WM / 16;
     constexpr int TN_ = BN / WN / 16;
-    constexpr int STAGE = (BM + BN) * G2_BK;  // bf16 elements per stage
-    __shared__ __attribute__((aligned(16))) bf16 lds[2 * STAGE];
+    constexpr int KS = G2_BK;                         // k-rows per LDS stage
+    constexpr int NST = TN ? tn_depth(BM, BN) : 2;    // LDS stages
+    constexpr int STAGE = (BM + BN) * KS;             // bf16 elements per stage
+    __shared__ __attribute__((aligned(16))) bf16 lds[NST * STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int nJ = (N + BN - 1) / BN;
-    const int L = xcd_remap(blockIdx.x, gridDim.x);
-    // tile order in groups of two row tiles: the 4 consecutive tiles an XCD
-    // takes (xcd_remap) form a 2 x 2 square, so each A row panel and each B
-    // column panel of a K-chunk is fetched by half as many XCDs as in row-major
-    // order (which shares A panels but sends every B panel to all eight)
     const int nI = (M + BM - 1) / BM;
-    int ti, tj;
-    {
-        const int gsz = 2 * nJ, grp = L / gsz, first = grp * 2, gm = min(nI - first, 2), r = L - grp * gsz;
-        ti = first + r % gm;
-        tj = r / gm;
+    int ti, tj, chunk = 0;
+    if (TN) {   // flat grid of tiles x slabs, chunk-major
+        tn_chunk_major(blockIdx.x, nI, nJ, gridDim.x / (nI * nJ), ti, tj, chunk);
+    } else {
+        tile_2row(xcd_remap(blockIdx.x, gridDim.x), nI, nJ, ti, tj);
     }
     const int i0 = ti * BM, j0 = tj * BN;
-    const int kbeg = blockIdx.y * kchunk;
+    const int kbeg = chunk * kchunk;
     const int kend = min(K, kbeg + kchunk);
     const int nk = kend > kbeg ? (kend - kbeg + G2_BK - 1) / G2_BK : 0;
 
@@ -537,51 +596,50 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_lds_kernel(
 
     auto stage = [&](int t, int buf) {
         bf16* img = lds + buf * STAGE;
-        const int k0 = kbeg + t * G2_BK;
+        const int k0 = kbeg + t * KS;
         if (TN) {
             stage_tn<BM>(A, lda, i0, M, k0, kend, img, wave, lane);
-            stage_tn<BN>(B, ldb, j0, N, k0, kend, img + BM * G2_BK, wave, lane);
+            stage_tn<BN>(B, ldb, j0, N, k0, kend, img + BM * KS, wave, lane);
         } else {
             stage_nt<BM>(A, lda, i0, M, k0 % ka, img, wave, lane);  // ka < K: A reused (split weight)
-            stage_nt<BN>(B, ldb, j0, N, k0, img + BM * G2_BK, wave, lane);
+            stage_nt<BN>(B, ldb, j0, N, k0, img + BM * KS, wave, lane);
         }
     };
-    if (nk > 0) stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int t = 0; t < nk; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < nk) stage(t + 1, cur ^ 1);
-        bf16* img = lds + cur * STAGE;
-        if (TN && kbeg + (t + 1) * G2_BK > kend) {
-            // partial last stage: k-rows past kend hold clamped copies -> zero them
-            // (uniform branch: every wave takes it or none)
-            const int valid = kend - kbeg - t * G2_BK;
-            for (int e = tid; e < (G2_BK - valid) * (BM + BN) / 8; e += GB_THREADS) {
-                const int per_a = (G2_BK - valid) * BM / 8;
-                bf16x8 z = {};
-                if (e < per_a) {
-                    *reinterpret_cast<bf16x8*>(img + valid * BM + e * 8) = z;
-                } else {
-                    *reinterpret_cast<bf16x8*>(img + BM * G2_BK + valid * BN + (e - per_a) * 8) = z;
-                }
-            }
-            __syncthreads();
-        }
-        const bf16* As = img;
-        const bf16* Bs = img + BM * G2_BK;
+    // TN: LDS byte addresses of the lane's fragment reads in stage 0, sub-step 0
+    uint32_t aoff[TM], boff[TN_];
+    if constexpr (TN) {
+        const uint32_t base = (uint32_t)(size_t)(lds_void*)lds;
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
+        for (int a = 0; a < TM; ++a) aoff[a] = base + tn_frag_off<BM>(wm * TM * 16 + a * 16, lane);
+#pragma unroll
+        for (int b = 0; b < TN_; ++b) boff[b] = base + 2 * BM * KS + tn_frag_off<BN>(wn * TN_ * 16 + b * 16, lane);
+    }
+    // the MFMAs of one landed stage, k sub-steps of 32 in ascending order
+    auto compute = [&](int buf) {
+        const bf16* As = lds + buf * STAGE;
+        const bf16* Bs = As + BM * KS;
+#pragma unroll
+        for (int s = 0; s < KS / 32; ++s) {
             bf16x8 af[TM], bfv[TN_];
+            if constexpr (TN) {
+                s16x4 alo[TM], ahi[TM], blo[TN_], bhi[TN_];
+                const uint32_t so = (uint32_t)buf * (2 * STAGE);
 #pragma unroll
-            for (int a = 0; a < TM; ++a) {
-                if (TN) af[a] = frag_tn<BM>(As, s, wm * TM * 16 + a * 16, lane);
-                else af[a] = frag_nt(As, wm * TM * 16 + a * 16 + (lane & 15), s * 4 + (lane >> 4));
-            }
+                for (int a = 0; a < TM; ++a) tn_read<BM>(aoff[a] + so + s * 64 * BM, alo[a], ahi[a]);
 #pragma unroll
-            for (int b = 0; b < TN_; ++b) {
-                if (TN) bfv[b] = frag_tn<BN>(Bs, s, wn * TN_ * 16 + b * 16, lane);
-                else bfv[b] = frag_nt(Bs, wn * TN_ * 16 + b * 16 + (lane & 15), s * 4 + (lane >> 4));
+                for (int b = 0; b < TN_; ++b) tn_read<BN>(boff[b] + so + s * 64 * BN, blo[b], bhi[b]);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int a = 0; a < TM; ++a) af[a] = tn_landed(alo[a], ahi[a]);
+#pragma unroll
+                for (int b = 0; b < TN_; ++b) bfv[b] = tn_landed(blo[b], bhi[b]);
+            } else {
+#pragma unroll
+                for (int a = 0; a < TM; ++a)
+                    af[a] = frag_nt(As, wm * TM * 16 + a * 16 + (lane & 15), s * 4 + (lane >> 4));
+#pragma unroll
+                for (int b = 0; b < TN_; ++b)
+                    bfv[b] = frag_nt(Bs, wn * TN_ * 16 + b * 16 + (lane & 15), s * 4 + (lane >> 4));
             }
 #pragma unroll
             for (int a = 0; a < TM; ++a)
@@ -589,12 +647,63 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_lds_kernel(
                 for (int b = 0; b < TN_; ++b)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfv[b], acc[a][b], 0, 0, 0);
         }
+    };
+    if constexpr (TN) {
+        // Ring of NST stages: stage t + NST - 1 is issued while stage t computes,
+        // so NST - 1 stages of DMA are in flight per workgroup. A K-step ends on
+        // a COUNTED vmcnt (stage t + 1 landed, the later ones stay in flight) and
+        // a raw s_barrier (__syncthreads would drain the DMA queue); the ring
+        // drains as the chunk ends. Stage t + NST - 1 lands in the slot stage
+        // t - 1 was read from, which every wave left at the previous barrier.
+        constexpr int P = (BM + BN) * KS / 8 / GB_THREADS;  // DMA instructions per thread and stage
+#pragma unroll
+        for (int u = 0; u < NST - 1; ++u)
+            if (u < nk) stage(u, u);
+        wait_dma<P, NST - 2>(min(NST - 2, nk - 1));
+        __builtin_amdgcn_s_barrier();
+        int cur = 0, nxt = NST - 1;
+        for (int t = 0; t < nk; ++t) {
+            if (t + NST - 1 < nk) stage(t + NST - 1, nxt);
+            bf16* img = lds + cur * STAGE;
+            if (kbeg + (t + 1) * KS > kend) {
+                // partial last K-step: k-rows past kend hold clamped copies -> zero
+                // them in the stage about to compute, which has landed (uniform
+                // branch: every wave takes it or none)
+                const int valid = kend - kbeg - t * KS;
+                for (int e = tid; e < (KS - valid) * (BM + BN) / 8; e += GB_THREADS) {
+                    const int per_a = (KS - valid) * BM / 8;
+                    bf16x8 z = {};
+                    if (e < per_a) {
+                        *reinterpret_cast<bf16x8*>(img + valid * BM + e * 8) = z;
+                    } else {
+                        *reinterpret_cast<bf16x8*>(img + BM * KS + valid * BN + (e - per_a) * 8) = z;
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+            }
+            compute(cur);
+            // stage t + 1 landed; stages t + 2 .. min(t + NST - 1, nk - 1) may stay in flight
+            wait_dma<P, NST - 2>(min(t + NST - 1, nk - 1) - (t + 1));
+            __builtin_amdgcn_s_barrier();
+            cur = cur + 1 == NST ? 0 : cur + 1;
+            nxt = nxt + 1 == NST ? 0 : nxt + 1;
+        }
+    } else {
+        if (nk > 0) stage(0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        for (int t = 0; t < nk; ++t) {
+            const int cur = t & 1;
+            if (t + 1 < nk) stage(t + 1, cur ^ 1);
+            compute(cur);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
     }
 
     float* out = C;
-    if (EPI == EPI_SLAB) out = C + (int64_t)blockIdx.y * M * N;
+    if (EPI == EPI_SLAB) out = C + (int64_t)chunk * M * N;
     if (EPI == EPI_STATS || EPI == EPI_STATS16) {
         // BatchNorm column partials from the fp32 accumulators
         const int cb = j0 + wn * TN_ * 16 + (lane & 15);
@@ -644,7 +753,7 @@ __global__ __launch_bounds__(GB_THREADS, 2) void gemm_lds_kernel(
     // moves 16-byte row pieces (4 fp32 or 8 bf16 outputs per store) instead of
     // scalar stores of 16-lane column fragments.
     constexpr int LDT = BN + 4;
-    constexpr int LDSB = 2 * STAGE * (int)sizeof(bf16);
+    constexpr int LDSB = NST * STAGE * (int)sizeof(bf16);
     constexpr int NR = BM * LDT * 4 <= LDSB ? 1 : 2;
     constexpr int RR = BM / NR;
     static_assert(RR * LDT * 4 <= LDSB && WM % NR == 0, "epilogue tile must fit the stage buffers");
@@ -1172,10 +1281,15 @@ int launch_gemm_lds(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, int 
     const int nJ = (N + BN - 1) / BN;
     constexpr bool can_half = EPI != EPI_STATS && EPI != EPI_STATS16;
     const bool half = lds_bm(M, N, BN, sp, EPI) == 64;
+    // split-K TN launches: a flat grid of tiles x slabs, decoded chunk-major (tn_chunk_major)
+    const auto grid_of = [](int tiles, int slabs) {
+        return TN ? dim3((unsigned)(tiles * slabs)) : dim3((unsigned)tiles, (unsigned)slabs);
+    };
+    const int slabs = EPI == EPI_SLAB ? sp : 1;
     if constexpr (can_half) {
         if (half) {
             const int nI = (M + 63) / 64;
-            dim3 grid((unsigned)(nI * nJ), (unsigned)(EPI == EPI_SLAB ? sp : 1));
+            const dim3 grid = grid_of(nI * nJ, slabs);
             hipLaunchKernelGGL((gemm_lds_kernel<TN, 64, BN, EPI>), grid, dim3(GB_THREADS), 0, st, A, lda, B, ldb, M,
                                N, K, EPI == EPI_SLAB ? kchunk : K, ka, C, ldc, part, addend, ldd);
             return hipGetLastError() == hipSuccess ? DGX_OK : DGX_ELAUNCH;
@@ -1183,7 +1297,7 @@ int launch_gemm_lds(const bf16* A, int64_t lda, const bf16* B, int64_t ldb, int 
     }
     {
         const int nI = (M + G2_BM - 1) / G2_BM;
-        dim3 grid((unsigned)(nI * nJ), (unsigned)(EPI == EPI_SLAB ? sp : 1));
+        const dim3 grid = grid_of(nI * nJ, slabs);
         hipLaunchKernelGGL((gemm_lds_kernel<TN, G2_BM, BN, EPI>), grid, dim3(GB_THREADS), 0, st, A, lda, B, ldb, M,
                            N, K, EPI == EPI_SLAB ? kchunk : K, ka, C, ldc, part, addend, ldd);
     }
@@ -1473,6 +1587,14 @@ int dgx_gemm_lds_tile(int tn, int M, int N, int K, int a_k, int epi, int splits)
     const int bn = lds_bn(N);
     const int slabs = tn ? dgx_split_k(K, splits, G2_BK).slabs : 1;  // NT launches never split
     return lds_bm(M, N, bn, slabs, epi) * 1000 + bn;
+}
+
+int dgx_gemm_lds_tn_map(int id, int nI, int nJ, int slabs) {
+    if (nI < 1 || nJ < 1 || slabs < 1 || id < 0 || (int64_t)nI * nJ * slabs > INT32_MAX || id >= nI * nJ * slabs)
+        return DGX_EINVAL;
+    int ti, tj, chunk;
+    tn_chunk_major(id, nI, nJ, slabs, ti, tj, chunk);
+    return chunk * nI * nJ + ti * nJ + tj;
 }
 
 int dgx_gemm_bf16(const void* A, int a_bf16, int a_ic, int64_t lda, const void* B, int b_bf16, int b_ic,

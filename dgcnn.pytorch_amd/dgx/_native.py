@@ -90,6 +90,7 @@ _SIGS = {
     "dgx_gemm_lds_slabs": [_i32, _i32],
     "dgx_gemm_f32_slabs": [_i32, _i32],
     "dgx_gemm_lds_tile": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "dgx_gemm_lds_tn_map": [_i32, _i32, _i32, _i32],
     "dgx_gemm_edge_dz_rows": [_i32, _i32],
     "dgx_gemm_edge_dz_bf16": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
                               _vp, _vp, _i32, _vp],

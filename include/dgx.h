@@ -463,6 +463,13 @@ int dgx_gemm_lds_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, in
  * negative code its shape checks return. Host arithmetic only: the launcher
  * takes its decision from the same functions. */
 int dgx_gemm_lds_tile(int tn, int M, int N, int K, int a_k, int epi, int splits);
+/* Workgroup map of a tn = 1 launch with nI x nJ output tiles and `slabs`
+ * K-chunks (a flat grid of nI * nJ * slabs workgroups): the (chunk, tile)
+ * workgroup `id` computes, as chunk * nI * nJ + ti * nJ + tj, or DGX_EINVAL.
+ * Chunk-major: workgroups id and id + 8 share an XCD and each XCD takes a
+ * contiguous range of chunk * tiles + tile, i.e. whole chunks. The kernel
+ * decodes its block id with the same function. Host arithmetic only. */
+int dgx_gemm_lds_tn_map(int id, int nI, int nJ, int slabs);
 /* fp32 (rows x cols, row stride lds) -> two bf16 planes (row stride ldo): hi =
  * bf16(x) (nullable: skip), lo = bf16(x - hi) — x with 16 significant bits as
  * hi + lo. The operands of the fp32 parity mode's 3-pass GEMMs (hi.W_hi +

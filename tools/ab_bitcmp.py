@@ -1,7 +1,8 @@
 """A/B bit comparison of two libdgx builds: `python tools/ab_bitcmp.py OUT.pt`
 runs one DGCNN train step (cfg2 geometry, bf16 and fp32 modes) with the build
 DGX_LIB names and saves output, gradients and BN buffers; `--compare A.pt B.pt`
-reports every tensor that differs."""
+reports every tensor that differs; `--compare-dirs A B` does the same for two
+`bench.py --dump-outputs` directories."""
 import sys
 import types
 
@@ -37,7 +38,24 @@ def compare(a, b):
     return 1 if bad else 0
 
 
+def compare_dirs(a, b):
+    """two `bench.py --dump-outputs` directories: every <name>.npy, byte for byte"""
+    import os
+
+    import numpy as np
+    names = sorted(f for f in os.listdir(a) if f.endswith(".npy"))
+    missing = sorted(set(names) ^ {f for f in os.listdir(b) if f.endswith(".npy")})
+    bad = [n for n in names if n not in missing and
+           np.load(os.path.join(a, n)).tobytes() != np.load(os.path.join(b, n)).tobytes()]
+    kinds = {k: sum(n.startswith(k) for n in names) for k in ("output", "param.", "grad.")}
+    print(f"{a} vs {b}: {len(names)} arrays {kinds}, {len(bad)} differ {bad[:20]}" +
+          (f", only in one: {missing}" if missing else ""))
+    return 1 if bad or missing or not names else 0
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--compare-dirs":
+        sys.exit(compare_dirs(sys.argv[2], sys.argv[3]))
     if sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
     run(sys.argv[1])
